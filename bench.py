@@ -3,16 +3,27 @@
 (2-D uniform thermal plasma, 1024x1024 cells, 64 ppc, 1 species, periodic; push + deposit + FDTD +
 guard handling + the periodic tile sort), synthetic inputs generated in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as ``python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...`` (one rank per GPU, RCCL): WEAK scaling -- every rank owns a 1024x1024 slab of a
 (1024*N)x1024 periodic box, x faces exchanged with the ring neighbours.
 
-Rank 0 prints ONE JSON line: metric/value (whole-job particle-updates/s), a ``roofline`` object
-for the dominant kernel (the tiled push+deposit kernel, timed live with HIP events on its stream)
-and, at N = 1, a ``cpu_baseline`` object (the oracle port timed on the host cores on a bounded
-sample of the same workload).
+Rank 0 prints ONE JSON line: metric/value (whole-job particle-updates/s), ``ms_per_step`` and a
+``roofline`` object for the dominant kernel (the tiled push+deposit kernel, timed live with HIP
+events on its stream inside the timed steps).  A plain run does nothing else: set-up, warm-up, the
+K timed steps, the line.
+
+``--dump-outputs DIR`` writes what the timed steps left behind -- the state an ``engine.run_steps``
+caller reads back: the ten field arrays and the particle attributes -- as ``DIR/<name>.npy`` (float64,
+fixed seeded samples of the large arrays, see ``dump_outputs``).  The inputs are seeded, so two builds
+of the library can be compared output for output.
+
+``--full`` adds everything else the benchmark measures, each in runs of its own after the headline:
+at N = 1 the ``extra`` C3 / C5-slab legs and the ``cpu_baseline`` object (the CPU path timed on the
+host cores on a bounded sample of the same workload, with the C1 parity figures); at N > 1 the
+fixed-size C2-strong, C4 and C5 slab legs.  ``--no-extra`` / ``--no-cpu-baseline`` take single pieces
+out of a ``--full`` run again.
 """
 from __future__ import annotations
 
@@ -265,6 +276,39 @@ def recorded_traffic(args, kernel_prefix):
     if tr.get("source_sha256_16") != source_hash():
         return None, "traffic profile predates the current kernel sources: re-run tools/prof_pmc.sh"
     return tr["traffic_bytes_per_launch"], f"recorded: profiles/r04_k1_traffic.json @ sources {tr['source_sha256_16']}"
+
+
+DUMP_FIELD_SAMPLE = 1 << 19      # elements kept of a field array larger than that (4 MiB of float64 each)
+DUMP_PARTICLE_SAMPLE = 1 << 18   # particles kept, about (selected by id: the slot order changes from sort to sort)
+
+
+def dump_outputs(eng, path):
+    """what a caller of the timed path reads back after its last step, as ``path/<name>.npy`` in float64, under 64 MB in
+    all: the ten padded field arrays of this rank's slab (a fixed, seeded sample of ``DUMP_FIELD_SAMPLE`` elements of
+    the flattened array where it is larger, the same indices for every field, ascending) and, per species, the attributes
+    of the live particles whose id is a multiple of a fixed stride, ordered by id (``<species>_id`` names them; slots
+    move with every sort, ids do not).  ``diagnostics()`` has run before: E is whole, inv_gamma is current."""
+    from lambdapic_amd.device import FIELD_ATTRS
+    os.makedirs(path, exist_ok=True)
+    g = eng.grid
+    ncell = g.buf[0].numel()
+    idx = None
+    if ncell > DUMP_FIELD_SAMPLE:
+        pick = np.sort(np.random.default_rng(20260722).permutation(ncell)[:DUMP_FIELD_SAMPLE])
+        idx = torch.from_numpy(pick).to(g.buf.device)
+    for name in FIELD_ATTRS:
+        flat = g.view(name).reshape(-1)
+        np.save(os.path.join(path, f"{name}.npy"), (flat if idx is None else flat[idx]).cpu().numpy().astype(np.float64))
+    for k, sp in enumerate(eng.species):
+        s = sp.cset
+        n = int(sp.n)
+        ident = s.id[:n] & ((1 << 40) - 1)                  # (the rank sits above bit 40)
+        stride = max(1, -(-n // DUMP_PARTICLE_SAMPLE))
+        keep = torch.nonzero((ident % stride == 0) & ~torch.isnan(s.arr("x")[:n])).reshape(-1)
+        keep = keep[torch.argsort(ident[keep])]
+        np.save(os.path.join(path, f"species{k}_id.npy"), s.id[:n][keep].cpu().numpy().astype(np.float64))
+        for name in ("x", "y", "ux", "uy", "uz", "inv_gamma", "w"):
+            np.save(os.path.join(path, f"species{k}_{name}.npy"), s.arr(name)[:n][keep].cpu().numpy().astype(np.float64))
 
 
 class StageTimer:
@@ -856,12 +900,18 @@ def main():
     ap.add_argument("--ppc", type=int, default=64)
     ap.add_argument("--sort-interval", type=int, default=20)
     ap.add_argument("--block-particles", type=int, default=8192)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (fields, particle attributes: see dump_outputs) "
+                         "as DIR/<name>.npy; with N > 1 every rank writes DIR/rank<r>/")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what else the benchmark measures: the C3 / C5-slab legs and the CPU "
+                         "baseline with the C1 parity figures (N = 1), the C2-strong, C4 and C5 slab legs (N > 1)")
     ap.add_argument("--cpu-cells", type=int, default=512)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / C5-slab legs (N = 1) / the C2-strong, C4 "
-                                                            "and C5 slab legs (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the C3 / C5-slab legs (N = 1) / the "
+                                                            "C2-strong, C4 and C5 slab legs (N > 1)")
     ap.add_argument("--leg-steps", type=int, default=0, help="timed steps of the N > 1 legs (default: 200 / 200 / 20)")
     ap.add_argument("--legs", default="c2s,c4,c5", help="which N > 1 legs to run")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -901,6 +951,8 @@ def main():
                          "kernel skips its rho atomics, a real deposit re-anchors rho on every sort step) or deposited "
                          "in every step like the reference's kernel")
     args = ap.parse_args()
+    if not args.full:                  # a plain run: the headline and nothing else
+        args.no_extra = args.no_cpu_baseline = True
 
     import torch.distributed as dist
     from lambdapic_amd.dist import SlabComm
@@ -1025,6 +1077,8 @@ def main():
     k_ms = float(np.sum([a.elapsed_time(b) for a, b in ev])) / args.steps if ev else float("nan")
     d = eng.diagnostics()
     alive = d["nalive"][0]
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{comm.rank}"))
     alg_bytes = BYTES_PER_PARTICLE * n_local + GATHER_SCATTER_BYTES_PER_CELL * args.nx * args.ny
     achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if ev else float("nan")
     traffic, traffic_source = recorded_traffic(args, "k_push_deposit_tiled_2d")

@@ -232,6 +232,48 @@ def test_bench_watchdog_prints_what_it_has_and_exits_nonzero():
     assert "exceeded its time budget" in r.stderr
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_ordered_by_id(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 .npy files; a field larger than the cap is the same seeded sample of its flattened
+    array for every field and every call; particles are picked by id (a multiple of the stride, live ones only) and
+    ordered by id, whatever slots the sort left them in"""
+    import types
+    import torch
+    import bench
+    from lambdapic_amd.fields import FIELD_ATTRS
+    monkeypatch.setattr(bench, "DUMP_FIELD_SAMPLE", 50)
+    monkeypatch.setattr(bench, "DUMP_PARTICLE_SAMPLE", 16)
+    buf = torch.arange(10 * 12 * 12, dtype=torch.float64).reshape(10, 12, 12)
+    grid = types.SimpleNamespace(buf=buf, view=lambda name: buf[FIELD_ATTRS.index(name)])
+    gen = torch.Generator().manual_seed(3)
+    names = ("x", "y", "ux", "uy", "uz", "inv_gamma", "w")
+
+    def species(order):
+        """the same 100 particles (attribute = function of the id) in the slots ``order`` gives them; 90 slots in use"""
+        ident = order + (3 << 40)
+        data = {a: (order.double() + 1) * (k + 1) for k, a in enumerate(names)}
+        data["x"][order == 14] = float("nan")            # a dead particle whose id the stride would pick
+        cset = types.SimpleNamespace(id=ident, arr=lambda a: data[a])
+        return types.SimpleNamespace(cset=cset, n=90)
+
+    first = torch.randperm(100, generator=gen)
+    second = torch.cat([first[:90][torch.randperm(90, generator=gen)], first[90:]])
+    out = []
+    for k, order in enumerate((first, second)):
+        bench.dump_outputs(types.SimpleNamespace(grid=grid, species=[species(order)]), str(tmp_path / str(k)))
+        out.append({f.stem: np.load(f) for f in sorted((tmp_path / str(k)).iterdir())})
+    a, b = out
+    assert sorted(a) == sorted(list(FIELD_ATTRS) + ["species0_id"] + [f"species0_{n}" for n in names])
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = (a["ex"] - buf[FIELD_ATTRS.index("ex")].min().item()).astype(int)
+    assert a["ex"].shape == (50,) and np.all(np.diff(idx) > 0)
+    assert all(np.array_equal(a[n], buf[FIELD_ATTRS.index(n)].reshape(-1).numpy()[idx]) for n in FIELD_ATTRS)
+    ids = a["species0_id"] - (3 << 40)
+    live = set(first[:90].tolist()) - {14}
+    assert ids.tolist() == sorted(i for i in live if i % 6 == 0)           # stride = ceil(90 / 16)
+    assert np.array_equal(a["species0_uy"], (ids + 1) * 4)
+
+
 def test_particle_message_window_follows_the_counts():
     """dist.MigrateWindowMixin: the part of the fixed-size particle face message that travels -- MARGIN x the largest
     count the ranks saw, a power of two between MIN and the capacity; grows at once, halves at most per retune; a step

@@ -9,7 +9,7 @@ TAG=r04_rehearse_n$N$(echo "$*" | tr -c 'a-z0-9\n' '_' | cut -c1-40)
 mkdir -p gpurun_out
 BACKEND="--backend gloo"; case "$*" in *--backend*) BACKEND="";; esac
 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus $N --steps 4 --warmup 2 $BACKEND --share-gpu --leg-steps $STEPS --legs $LEGS "$@" \
+  bench.py --gpus $N --steps 4 --warmup 2 --full $BACKEND --share-gpu --leg-steps $STEPS --legs $LEGS "$@" \
   > gpurun_out/$TAG.json.log 2> gpurun_out/$TAG.err
 rc=$?
 echo "exit code $rc" | tee -a gpurun_out/$TAG.err
