@@ -763,6 +763,69 @@ typedef struct {
 #define LPA_STAGE_E2 7
 int lpa_step(const lpa_step_desc *d, int first_stage, int last_stage, void *stream);
 
+/* ---- relativistic binary Coulomb collisions (replaces Collision.__call__ / calculate_debye_length,
+ *      core/collision/collision.py:153-207, i.e. intra_collision_patches / inter_collision_patches and
+ *      debye_length_patches + constrain_debye_length_patches, core/collision/cpu.py:136-250,281-371, with the pairing
+ *      iterators of core/collision/utils.py:233-419).  One launch per species pair: a workgroup per 256-cell tile, a
+ *      wave per cell, a lane per pair (csrc/lpa_collide.hip).
+ *
+ *      INPUTS: stores a tile sort has just produced with ahead = 0 -- [0, n_sorted) tile ordered, every live particle
+ *      in the tile of its nearest-node cell.  Only lpa_tiling.tile_off is relied on (any LPA_ORDER_*); a particle's
+ *      collision cell is the sort's cell of its current x, y(, z).  A live particle whose cell is not in its tile is
+ *      left alone and counted in `skipped`; NaN-position / is_dead slots are ignored.  `id` must be set (LPA_ERR_ARG
+ *      otherwise) and unique per species.  gamma is sqrt(1 + u^2) of the momenta, never read from inv_gamma, which
+ *      may be NULL (LPA_PUSH_NO_IG stores) and is written (for the updated particles) only where it is set.
+ *
+ *      PAIRING CONTRACT (defined on ids: independent of the storage order, restart-exact without generator state):
+ *       - R(c0, c1, c2, c3) = Philox-4x32-10, key = (seed low word, seed high word); multipliers 0xD2511F53,
+ *         0xCD9E8D57, Weyl 0x9E3779B9, 0xBB67AE85 (counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8);
+ *         U(lo, hi) = (((uint64)hi << 32 | lo) >> 11) * 2^-53.
+ *       - canonical order of a species' live particles in a cell: ascending id.  Shuffled order: ascending
+ *         (key, id), key = w0 | w1 << 32 of R(id_lo, id_hi, itime, pair_index << 8 | side), side 0 = a, 1 = b.
+ *       - intra-species (n >= 2, shuffled list s): npairs = (n + 1) / 2, pair k = (s[2k], s[2k+1]); odd n: the last
+ *         pair is (s[n-1], s[0]) and the first and last pair carry w_corr = 1/2; dt_corr = 2 npairs - 1
+ *         (utils.py:233-293).
+ *       - inter-species (n1, n2 >= 1): the larger side is shuffled (ties: species a), the other canonical; npairs =
+ *         nmax; pair i = (shuffled[i], canonical[i mod nmin]), particle 1 of the pair is always the one of species a;
+ *         w_corr = 1 / (nmax / nmin + 1) if i mod nmin < nmax mod nmin, else 1 / (nmax / nmin); dt_corr = npairs
+ *         (utils.py:327-419).
+ *       - draws of pair i in cell c (global index ix ny + iy, or (ix ny + iy) nz + iz): R(i, c, itime,
+ *         pair_index << 8 | 2) -> U_theta = U(w0, w1), phi = 2 pi U(w2, w3); R(i, c, itime, pair_index << 8 | 3) ->
+ *         U_acc = U(w0, w1).  Indexed, not consumed: a pair at rest (p1_com == 0) skips without shifting a number.
+ *       - pair physics: collision_data, coulomb_scattering, rotate_momentum, boost_to_lab, varying_lnLambda and the
+ *         accept rule of collision_kernel (utils.py:26-205, cpu.py:252-278,374-428): weights w w_corr, Nanbu's fit
+ *         below s = 4 and isotropic scattering from there, the p_perp > 1e-10 p branch, species a updated if
+ *         w_b' / w_max > U_acc, species b if w_a' / w_max > U_acc.
+ *       - within a cell the pairs act in ascending i, each seeing what earlier pairs left; species pairs act in the
+ *         order of the calls; the Debye arrays are computed once, before the first pair of a step.
+ *
+ *      lpa_collide_debye: inv_d2 / ntot (device, cell shaped: [nx][ny]([nz]), no guards) = sum over ALL species
+ *      passed of n q^2 / (eps0 kT) and of n, reset by the first species, floored with the summed density by the last
+ *      (rmin^2 = (4 pi n / 3)^(-2/3)).  p / t / q / m are HOST arrays of `nspecies` entries; every store must be
+ *      freshly sorted like lpa_collide's (no loose slots: n == n_sorted; a live particle outside the tile of its cell
+ *      is left out of the sums and counted in `skipped`, optional device uint32[1]).  The per-cell sums are FP64 LDS
+ *      atomics: their last bits depend on the arrival order. */
+typedef struct {
+    double dt;            /* time the collisions cover (the caller's dt times its collision interval)        */
+    double lnLambda;      /* Coulomb logarithm; <= 0: varying (varying_lnLambda), inv_d2 is then required     */
+    double eps0;          /* scipy.constants.epsilon_0 of the host environment (as for lpa_fdtd_e_*)          */
+    const double *inv_d2; /* lpa_collide_debye's first array, or NULL                                         */
+    uint64_t seed;
+    uint32_t itime;
+    uint32_t pair_index;
+    uint32_t *skipped;    /* optional device uint32[1], added to                                              */
+} lpa_collide_params;
+/* bytes of the `workspace` of lpa_collide for stores of these many tile-ordered slots (20 bytes per slot: the cell
+ * lists of (key, id, slot)) */
+int64_t lpa_collide_workspace_bytes(const lpa_grid *g, int64_t capacity_a, int64_t capacity_b);
+int lpa_collide_debye(const lpa_grid *g, int32_t nspecies, const lpa_particles *const *p, const lpa_tiling *const *t,
+                      const double *q, const double *m, double eps0, double *inv_d2, double *ntot, uint32_t *skipped,
+                      void *stream);
+/* pa == pb (and ta == tb) selects the intra-species form */
+int lpa_collide(const lpa_grid *g, const lpa_particles *pa, const lpa_tiling *ta, double qa, double ma,
+                const lpa_particles *pb, const lpa_tiling *tb, double qb, double mb, const lpa_collide_params *cp,
+                void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- diagnostics the parity contract is stated on (field energy, kinetic energy, total
  *      charge; reference tests/test_numerical_heating.py:19-50).  out[] is device memory and is
  *      accumulated into (zero it first).

@@ -113,6 +113,11 @@ class lpa_step_desc(C.Structure):
                 ("slab", C.POINTER(lpa_step_slab)), ("absorbed_spill", C.c_void_p)]
 
 
+class lpa_collide_params(C.Structure):
+    _fields_ = [("dt", C.c_double), ("lnLambda", C.c_double), ("eps0", C.c_double), ("inv_d2", C.c_void_p),
+                ("seed", C.c_uint64), ("itime", C.c_uint32), ("pair_index", C.c_uint32), ("skipped", C.c_void_p)]
+
+
 LPA_COMM_RCCL, LPA_COMM_LOOPBACK = 1, 2
 LPA_STEP_DEFER_E2_GUARDS, LPA_STEP_DEFER_E2, LPA_STEP_E1_DOUBLE = 1, 2, 4
 LPA_STEP_B_EXT_LO, LPA_STEP_B_EXT_HI, LPA_STEP_E_ROUND_IN_LINE, LPA_STEP_SEPARATE_UNPACK, LPA_STEP_SEPARATE_PACK, LPA_STEP_SEPARATE_TAILS = 8, 16, 32, 64, 128, 256
@@ -212,6 +217,10 @@ SIGNATURES = {
     "lpa_comm_info": (_i, [_vp, C.POINTER(C.c_int32)]),
     "lpa_comm_exchange": (_i, [_vp, C.POINTER(lpa_face_msg), C.c_int32, _vp]),
     "lpa_step": (_i, [C.POINTER(lpa_step_desc), _i, _i, _vp]),
+    "lpa_collide_workspace_bytes": (_i64, [_G, _i64, _i64]),
+    "lpa_collide_debye": (_i, [_G, C.c_int32, C.POINTER(_P), C.POINTER(_T), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               _d, _vp, _vp, _vp, _vp]),
+    "lpa_collide": (_i, [_G, _P, _T, _d, _d, _P, _T, _d, _d, C.POINTER(lpa_collide_params), _vp, _i64, _vp]),
     "lpa_diag_fields": (_i, [_G, _d, _d, _vp, _vp]),
     "lpa_diag_particles": (_i, [_P, _d, _vp, _vp]),
     "lpa_refresh_inv_gamma": (_i, [_P, _i64, _i64, _vp]),

@@ -15,7 +15,11 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "liblambdapic_amd.so"
 SOURCES = ["lpa_fields.hip", "lpa_particles.hip", "lpa_particles3d.hip", "lpa_sort.hip", "lpa_patches.hip",
-           "lpa_rho.hip", "lpa_step.hip", "lpa_patches3d.hip", "lpa_comm.hip"]
+           "lpa_rho.hip", "lpa_step.hip", "lpa_patches3d.hip", "lpa_comm.hip", "lpa_collide.hip"]
+# per-source flags.  lpa_collide.hip is FP64 and integer code throughout: the packed-FP32 target feature is switched off
+# for it so that no v_pk_{add,mul,fma}_f32 can be selected for it whatever a later compiler vectorises (none is needed;
+# the older sources keep the flags they were measured with)
+SOURCE_FLAGS = {"lpa_collide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function"]
 
@@ -61,7 +65,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=()) -> Path:
         src, obj = CSRC / s, objdir / (s + ".o")
         objs.append(obj)
         if force or not obj.exists() or obj.stat().st_mtime < max(src.stat().st_mtime, newest_hdr):
-            cmd = [_hipcc(), *FLAGS, *extra_flags, "-c", str(src), "-o", str(obj)]
+            cmd = [_hipcc(), *FLAGS, *SOURCE_FLAGS.get(s, ()), *extra_flags, "-c", str(src), "-o", str(obj)]
             if verbose:
                 print(" ".join(cmd))
             procs.append((s, subprocess.Popen(cmd)))

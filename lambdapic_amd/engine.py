@@ -31,6 +31,7 @@ from . import _lib, constants
 from ._lib import LPA_MIG_NATTR, check, lib
 from .device import DeviceGrid2D, DeviceParticles, current_stream_ptr, restore_device, to_host
 from .dist import MigrateWindowMixin, SlabComm, exchange_faces
+from .collision import CollisionMixin
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
 
@@ -128,7 +129,7 @@ class DevicePML2D:
         return self._coef[k]
 
 
-class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
+class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin):
     dim = 2
 
     def __init__(self, nx, ny, dx, dy, n_guard=3, device="cuda:0", comm: SlabComm | None = None,
@@ -292,7 +293,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
 
     # ---- restart (RestartDump, `callback/restart.py:88-107`: the reference pickles the whole Simulation) ----
     _TRANSIENT = ("L", "_ws", "_halo", "_side", "_axes", "_diag", "_keep", "kernel_events", "_absorbed", "_jx_plane",
-                  "_one", "_step_keep", "_event_pool")
+                  "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches")
 
     def __getstate__(self):
         """everything but handles and scratch: the library handle, sort workspaces (and with them the tilings),
@@ -524,6 +525,8 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
         """look-ahead time of the sort (lpa_sort_tiles_ahead_*): half the interval the controller runs the store on, once
         that is shorter than ``sort_interval`` -- i.e. its particles outrun the tile margin.  Cold stores: 0 (the plain
         sort, two attribute streams less in its count pass)."""
+        if self._coll_sorting:
+            return 0.0          # a collision step pairs the particles of a cell: binned by where they ARE
         now = sp.get("sort_interval_now") if isinstance(sp, dict) else getattr(sp, "sort_interval_now", None)
         if self.comm.size > 1:          # a slab chain sorts on its common clock
             now = self._chain_interval()
@@ -645,6 +648,21 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
         fs.count, fs.slot = ws["fs_count"].data_ptr(), ws["fs_slot"].data_ptr()
         fs.edge_cols, fs.depth = cols, self.FREE_SLOT_DEPTH
         ws["fs"] = fs
+
+    # ---- hooks of CollisionMixin (collision.py) ---------------------------------------------------
+    def _coll_store(self, i):
+        sp = self.species[i]
+        pc = sp.cset.cstruct(sp.n, eb=False)
+        if sp.ig_stale:           # (LPA_PUSH_NO_IG stores: the array is rebuilt from the momenta by whoever reads it)
+            pc.inv_gamma = None
+        return pc, sp.tiling, sp.q, sp.m
+
+    def _coll_fresh(self, i):
+        sp = self.species[i]
+        return sp.n == 0 or (sp.tiling is not None and sp.steps_since_sort == 0 and getattr(sp, "sort_ahead_used", 1.0) == 0.0)
+
+    def _coll_ncells(self):
+        return self.nx * self.ny
 
     def _ws_checked(self, sp):
         ws = self._sort_ws(sp)
@@ -1173,6 +1191,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
         self.update_bfield(0.5 * dt)
         self.sync_guard_fields(B)
         if tiled:
+            self._collision_stage(dt)
             for i, sp in enumerate(self.species):
                 if self.sort_due(sp):
                     self.sort(i)

@@ -26,6 +26,7 @@ from .device import restore_device, to_host
 from .dist import MigrateWindowMixin, SlabComm, exchange_faces
 from .engine import PicEngine2D, psi_ptr, psi_rows
 from .fields import FIELD_ATTRS, from_device_layout, to_device_layout
+from .collision import CollisionMixin
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
 
@@ -117,7 +118,7 @@ class DevicePML3D:
         return self._coef[k]
 
 
-class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
+class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin):
     dim = 3
     DEFAULT_ORDER = _lib.LPA_ORDER_STRIPED   # the in-tile order new engines sort to (LPA_ORDER_*)
 
@@ -267,7 +268,7 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
 
     # ---- restart (RestartDump, `callback/restart.py:88-107`) ------------------------------------------------
     _TRANSIENT = ("L", "c", "buf", "species", "_halo", "_side", "_axes", "_diag", "_keep", "kernel_events", "_absorbed",
-                  "_jx_plane", "_one", "_step_keep", "_event_pool")
+                  "_jx_plane", "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches")
 
     def __getstate__(self):
         """see PicEngine2D.__getstate__: fields and the slots in use of every store as host arrays, handles,
@@ -407,6 +408,18 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
                         "overflow": torch.empty(max(cap, 1), dtype=torch.int32, device=self.device),
                         "counters": cnt, "count": cnt[0:1], "tiling": _lib.lpa_tiling(), "mig": None}
         return sp["ws"]
+
+    # ---- hooks of CollisionMixin (collision.py) ---------------------------------------------------
+    def _coll_store(self, i):
+        sp = self.species[i]
+        return sp["c"], sp["tiling"], sp["q"], sp["m"]
+
+    def _coll_fresh(self, i):
+        sp = self.species[i]
+        return sp["n"] == 0 or (sp["tiling"] is not None and sp["since"] == 0 and sp.get("sort_ahead_used", 1.0) == 0.0)
+
+    def _coll_ncells(self):
+        return self.n[0] * self.n[1] * self.n[2]
 
     deep_tail_fraction = 0.005   # see PicEngine2D.sort
     sort_lookahead = True
@@ -1057,6 +1070,7 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin):
         self.sync_guard_fields(1)
         self.update_bfield(0.5 * dt)
         self.sync_guard_fields(2)
+        self._collision_stage(dt)
         self.reset_current()
         if not (self.overlap and self.push_deposit_overlapped(dt)):
             for i in range(len(self.species)):

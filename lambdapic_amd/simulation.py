@@ -16,7 +16,8 @@ The device owns the state; ``sim.patches[i].fields.*`` / ``.particles[ispec].*``
 λPIC's layout.  They are refreshed (device -> host) before a stage that has a triggered callback and
 written back (host -> device) after it, so reference-style callbacks run unchanged.  CPML layers,
 laser injection (``lambdapic_amd.laser``) and the moving window are device native.  Out of scope here
-(SURVEY.md section 2): QED, collisions, load balancing, I/O.  The 3-D twin is ``simulation3d.py``.
+(SURVEY.md section 2): QED, load balancing, I/O.  Binary Coulomb collisions are device native too
+(``add_collision``, ``lambdapic_amd.collision``; single slab).  The 3-D twin is ``simulation3d.py``.
 """
 from __future__ import annotations
 
@@ -26,6 +27,7 @@ import numpy as np
 import torch
 
 from . import constants
+from .collision import SimulationCollisionMixin
 from .dist import SlabComm
 from .engine import PicEngine2D
 from .patch import make_patches_2d
@@ -460,7 +462,7 @@ class MovingWindow:
             sim.shift_window_left(inject)
 
 
-class Simulation:
+class Simulation(SimulationCollisionMixin):
     """2-D periodic simulation driver with the reference's constructor vocabulary
     (`simulation/simulation.py:118-168`) and stage list (`:170-184`)."""
 
@@ -546,6 +548,7 @@ class Simulation:
         self.current_depositor = CurrentDeposition2D(self)
         self.pusher = [BorisPusher(self, i) for i in range(len(self.species))]
         self.sorter = [ParticleSort2D(self, i) for i in range(len(self.species))]
+        self._init_collision()
         self.initialized = True
 
     def _next_ids(self, ispec):
@@ -793,6 +796,7 @@ class Simulation:
             self.maxwell.update_bfield(0.5 * self.dt)
             self.patches.sync_guard_fields(B)
             self._run_stage(table, "maxwell_1")
+            self.engine._collision_stage(self.dt)      # (`simulation.py:974-978`; nothing without add_collision)
             for ispec in range(len(self.species)):
                 self.ispec = ispec
                 self.sorter[ispec]()

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import constants
+from .collision import SimulationCollisionMixin
 from .dist import SlabComm
 from .engine3d import ATTRS3, NROWS3, SIDES3, PicEngine3D
 from .fields import FIELD_ATTRS, Fields3D, from_device_layout, to_device_layout
@@ -95,7 +96,7 @@ class DevicePatches3D:
             self.sim.engine.sync_particles(i)
 
 
-class Simulation3D:
+class Simulation3D(SimulationCollisionMixin):
     STAGES = ["init", "start", "maxwell_1", "_push_position_1", "_interpolator", "_qed", "_push_momentum",
               "_push_position_2", "current_deposition", "qed_create_particles", "_laser", "maxwell_2", "end",
               "final"]
@@ -133,6 +134,7 @@ class Simulation3D:
             self.species.append(s)
 
     # ---- initialisation -----------------------------------------------------------------------------------
+
     def initialize(self):
         nxl = self.nx // self.comm.size
         self.engine = PicEngine3D(nxl, self.ny, self.nz, self.dx, self.dy, self.dz, self.n_guard, self.device,
@@ -174,6 +176,7 @@ class Simulation3D:
         self.maxwell = MaxwellSolver3D(self)
         self.pusher = [BorisPusher3D(self, i) for i in range(len(self.species))]
         self.sorter = [ParticleSort3D(self, i) for i in range(len(self.species))]
+        self._init_collision()
         self.initialized = True
 
     def _seed(self, s, org):
@@ -354,6 +357,7 @@ class Simulation3D:
             self.maxwell.update_bfield(0.5 * self.dt)
             self.patches.sync_guard_fields(B)
             self._run_stage(table, "maxwell_1")
+            eng._collision_stage(self.dt)      # (`simulation.py:974-978`; nothing without add_collision)
             for ispec in range(len(self.species)):
                 self.sorter[ispec]()
             eng.reset_current()

@@ -145,6 +145,7 @@ class FusedStepMixin:
                 for a, ax in enumerate(axes):
                     arr[a] = C.pointer(ax)
         if first <= _lib.LPA_STAGE_RESET <= last:
+            self._collision_stage(dt)       # (collision.py: nothing unless add_collision was called and a step is due)
             for i in self.sort_due_species():
                 self.sort(i)
             self._decide_phase()
