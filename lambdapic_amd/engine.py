@@ -32,6 +32,7 @@ from ._lib import LPA_MIG_NATTR, check, lib
 from .device import DeviceGrid2D, DeviceParticles, current_stream_ptr, restore_device, to_host
 from .dist import MigrateWindowMixin, SlabComm, exchange_faces
 from .collision import CollisionMixin
+from .patch import open_face_bounds
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
 
@@ -134,9 +135,14 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def __init__(self, nx, ny, dx, dy, n_guard=3, device="cuda:0", comm: SlabComm | None = None,
                  x0=0.0, y0=0.0, sort_interval=8, block_particles=8192, migrate_capacity=32768,
-                 boundary_conditions=None, cpml_thickness=6, order=_lib.LPA_ORDER_STRIPED):
+                 boundary_conditions=None, cpml_thickness=6, order=_lib.LPA_ORDER_STRIPED, absorb_bounds=None):
         """``nx`` is the LOCAL number of cells along x (this rank's slab); the global box has
-        ``nx * comm.size`` cells and this slab starts at ``x0 + rank*nx*dx``."""
+        ``nx * comm.size`` cells and this slab starts at ``x0 + rank*nx*dx``.
+
+        ``absorb_bounds``: per axis the ``(lo, hi)`` between which a particle survives an open (PML) axis, from
+        ``patch.open_face_bounds``.  The reference's bounds depend on its patch count in the last bit, so a caller that
+        has one (the ``Simulation`` facade) hands them over; a bare engine uses the ``npatch = 1`` form of the same
+        expression, ``((x0 + (n - 1) dx) - t dx) + dx / 2``."""
         self.L = lib()
         bc = dict(boundary_conditions or {k: "periodic" for k in ("xmin", "xmax", "ymin", "ymax")})
         for axis in "xy":
@@ -177,15 +183,12 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         # thickness (core/patch/patch.py:105-148) and a particle beyond them has no neighbour to go to
         self.absorb = 0
         self.alo, self.ahi = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
-        t = self.cpml_thickness
-        if not self.periodic_x:
-            self.absorb |= _lib.LPA_ABSORB_X
-            self.alo[0] = self.x0_global + t * self.dx - self.dx / 2
-            self.ahi[0] = self.x0_global + (self.nx * self.comm.size - 1 - t) * self.dx + self.dx / 2
-        if not self.periodic_y:
-            self.absorb |= _lib.LPA_ABSORB_X << 1
-            self.alo[1] = self.y0 + t * self.dy - self.dy / 2
-            self.ahi[1] = self.y0 + (self.ny - 1 - t) * self.dy + self.dy / 2
+        own = (open_face_bounds(self.x0_global, self.nx * self.comm.size, self.dx, self.cpml_thickness),
+               open_face_bounds(self.y0, self.ny, self.dy, self.cpml_thickness))
+        for a, periodic in enumerate((self.periodic_x, self.periodic_y)):
+            if not periodic:
+                self.absorb |= _lib.LPA_ABSORB_X << a
+                self.alo[a], self.ahi[a] = (float(v) for v in (absorb_bounds[a] if absorb_bounds else own[a]))
         self.eps0, self.mu0 = constants.EPSILON_0, constants.MU_0
         self._ws = {}
         self._halo = None

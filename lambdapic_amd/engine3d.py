@@ -26,6 +26,7 @@ from .device import restore_device, to_host
 from .dist import MigrateWindowMixin, SlabComm, exchange_faces
 from .engine import PicEngine2D, psi_ptr, psi_rows
 from .fields import FIELD_ATTRS, from_device_layout, to_device_layout
+from .patch import open_face_bounds
 from .collision import CollisionMixin
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
@@ -124,9 +125,12 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def __init__(self, nx, ny, nz, dx, dy, dz, n_guard=3, device="cuda:0", tiled=None, sort_interval=10,
                  block_particles=4096, comm=None, migrate_capacity=32768, boundary_conditions=None,
-                 cpml_thickness=6):
+                 cpml_thickness=6, absorb_bounds=None):
         """``nx`` = cells of THIS rank's slab along x; the box is ``nx * comm.size`` cells long.
-        ``boundary_conditions``: {'xmin': 'pml' | 'periodic', ...} for the six faces (default: periodic)"""
+        ``boundary_conditions``: {'xmin': 'pml' | 'periodic', ...} for the six faces (default: periodic).
+        ``absorb_bounds``: per axis the ``(lo, hi)`` between which a particle survives an open axis, as for
+        ``PicEngine2D``: handed over by a caller that knows the reference's patch count; a bare engine uses the
+        ``npatch = 1`` form, ``(((n - 1) d) - t d) + d / 2``."""
         bc = dict(boundary_conditions or {k: "periodic" for k in SIDES3})
         for ax in "xyz":
             if (bc[ax + "min"] == "periodic") != (bc[ax + "max"] == "periodic"):
@@ -184,9 +188,8 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         for a in range(3):
             if not self.periodic[a]:
                 self.absorb |= _lib.LPA_ABSORB_X << a
-                t = self.cpml_thickness
-                self.alo[a] = t * self.d[a] - self.d[a] / 2
-                self.ahi[a] = (ntot[a] - 1 - t) * self.d[a] + self.d[a] / 2
+                own = open_face_bounds(0.0, ntot[a], self.d[a], self.cpml_thickness)
+                self.alo[a], self.ahi[a] = (float(v) for v in (absorb_bounds[a] if absorb_bounds else own))
         self.species = []
         self._id_next = {}       # per species: ids issued by this rank so far (new_ids)
         self.eps0, self.mu0 = constants.EPSILON_0, constants.MU_0

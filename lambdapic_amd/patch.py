@@ -77,6 +77,61 @@ OFFSET_3D = {b: _offset_3d(b) for b in Boundary3D}
 OPPOSITE_3D = {b: next(o for o in Boundary3D if OFFSET_3D[o] == tuple(-v for v in OFFSET_3D[b])) for b in Boundary3D}
 
 
+class PMLFace:
+    """what the ownership bounds read of a PML object attached to a patch (`core/boundary/cpml.py`): the face it sits on
+    (``"xmin"`` ... ``"zmax"``) and its thickness in cells"""
+
+    def __init__(self, boundary: str, thickness: int):
+        assert boundary in ("xmin", "xmax", "ymin", "ymax", "zmin", "zmax")
+        self.boundary, self.thickness = boundary, int(thickness)
+
+
+def get_pml(pml_boundary, boundary: str):
+    """first entry of ``pml_boundary`` that sits on ``boundary`` (`core/boundary/utils.py:29-38`): a ``PMLFace``, or an
+    object of a class named like the reference's (``PMLXmin`` ... ``PMLZmax``, or derived from one)"""
+    cls_name = "PML" + boundary[0].upper() + boundary[1:]
+    for pml in pml_boundary:
+        if getattr(pml, "boundary", None) == boundary or any(c.__name__ == cls_name for c in type(pml).__mro__):
+            return pml
+    return None
+
+
+def _bound(axis: str, upper: bool):
+    """particle ownership bound of a patch along ``axis`` (`core/patch/patch.py:105-148`): node 0 / node n - 1, pulled in
+    by the thickness of a PML on that face -- in the reference's operation order, the result is compared bit for bit"""
+    def get(self):
+        o, n, d = getattr(self, axis + "0"), getattr(self, "n" + axis), getattr(self, "d" + axis)
+        pml = get_pml(self.pml_boundary, axis + ("max" if upper else "min"))
+        if upper:
+            v = o + (n - 1) * d
+            return v - pml.thickness * d if pml else v
+        return o + pml.thickness * d if pml else o
+    return property(get)
+
+
+def open_face_bounds(origin, n, d, thickness, npatch=1):
+    """(lo, hi) between which a particle survives along an axis with PML on both faces: ``xmin`` of the first and ``xmax``
+    of the last of ``npatch`` patches over ``n`` cells, each widened by half a cell (`core/patch/sync_particles_2d.c:236-241`).
+    Same operations in the same order as the reference -- the last patch starts at ``(npatch - 1) * L / npatch``
+    (`simulation/simulation.py:482`), its last node is pulled in by the layer (`core/patch/patch.py:116-120`) -- because
+    the result depends on it in the last bit (dx = 5e-8, n = 96, thickness 6: npatch = 1 and npatch = 3 differ by one ulp)."""
+    L = n * d
+    last = origin + (npatch - 1) * L / npatch
+    lo = (origin + thickness * d) - 0.5 * d
+    hi = ((last + (n // npatch - 1) * d) - thickness * d) + 0.5 * d
+    return lo, hi
+
+
+def _attach_pml_faces(patch, npatch, boundary_conditions, thickness):
+    """a PML on every face of ``patch`` that lies on a non-periodic face of the box (`simulation/simulation.py:455-463`)"""
+    for ax, n in zip("xyz", npatch):
+        i = getattr(patch, "ipatch_" + ax)
+        if boundary_conditions[ax + "min"] == "pml" and i == 0:
+            patch.pml_boundary.append(PMLFace(ax + "min", thickness))
+        if boundary_conditions[ax + "max"] == "pml" and i == n - 1:
+            patch.pml_boundary.append(PMLFace(ax + "max", thickness))
+
+
 class Patch3D:
     """attribute contract of the reference's ``Patch3D`` (`core/patch/patch.py:298-386`) the extensions read"""
 
@@ -93,12 +148,9 @@ class Patch3D:
         self.particles = []
         self.fields = None
 
-    xmin = property(lambda self: self.x0)
-    ymin = property(lambda self: self.y0)
-    zmin = property(lambda self: self.z0)
-    xmax = property(lambda self: self.x0 + (self.nx - 1) * self.dx)
-    ymax = property(lambda self: self.y0 + (self.ny - 1) * self.dy)
-    zmax = property(lambda self: self.z0 + (self.nz - 1) * self.dz)
+    xmin, xmax = _bound("x", False), _bound("x", True)
+    ymin, ymax = _bound("y", False), _bound("y", True)
+    zmin, zmax = _bound("z", False), _bound("z", True)
 
     def set_fields(self, fields):
         self.fields = fields
@@ -124,22 +176,9 @@ class Patch2D:
         self.particles = []
         self.fields = None
 
-    # particle ownership bounds; PML shrink (`patch.py:105-148`) arrives with the CPML row
-    @property
-    def xmin(self):
-        return self.x0
-
-    @property
-    def xmax(self):
-        return self.x0 + (self.nx - 1) * self.dx
-
-    @property
-    def ymin(self):
-        return self.y0
-
-    @property
-    def ymax(self):
-        return self.y0 + (self.ny - 1) * self.dy
+    # particle ownership bounds, with the PML shrink
+    xmin, xmax = _bound("x", False), _bound("x", True)
+    ymin, ymax = _bound("y", False), _bound("y", True)
 
     def set_fields(self, fields):
         self.fields = fields
@@ -258,9 +297,11 @@ def init_rect_neighbor_index_3d(patches, npatch, boundary_conditions):
             p.neighbor_rank[b] = 0
 
 
-def make_patches_3d(n, d, npatch, n_guard=3, boundary_conditions=None, nspecies=1):
+def make_patches_3d(n, d, npatch, n_guard=3, boundary_conditions=None, nspecies=1, cpml_thickness=None):
     """the rectangular 3-D patch set of the reference's ``Simulation3D.create_patches`` (`simulation/simulation.py:1143-1292`
-    for the in-scope parts): ``n`` = global cells, ``npatch`` = patches per axis, x fastest in the patch index"""
+    for the in-scope parts): ``n`` = global cells, ``npatch`` = patches per axis, x fastest in the patch index.  With
+    ``cpml_thickness`` the patches on a ``"pml"`` face of the box carry a ``PMLFace`` of that thickness, which pulls their
+    ownership bounds in."""
     from .fields import Fields3D
     from .particles import ParticlesBase
 
@@ -276,6 +317,8 @@ def make_patches_3d(n, d, npatch, n_guard=3, boundary_conditions=None, nspecies=
                 p.set_fields(Fields3D(*npp, *d, *org, n_guard))
                 for _ in range(nspecies):
                     p.add_particles(ParticlesBase(ipatch=p.index, rank=0))
+                if cpml_thickness is not None:
+                    _attach_pml_faces(p, npatch, bc, cpml_thickness)
                 patches.append(p)
     init_rect_neighbor_index_3d(patches.patches, npatch, bc)
     for a, ax in enumerate("xyz"):
@@ -285,9 +328,10 @@ def make_patches_3d(n, d, npatch, n_guard=3, boundary_conditions=None, nspecies=
 
 
 def make_patches_2d(nx, ny, dx, dy, npatch_x, npatch_y, n_guard=3, boundary_conditions=None,
-                    nspecies=1):
+                    nspecies=1, cpml_thickness=None):
     """Build the rectangular patch set the reference's ``Simulation.create_patches`` +
-    ``_init_fields`` produce (`simulation/simulation.py:432-448,467-502`)."""
+    ``_init_fields`` produce (`simulation/simulation.py:432-448,467-502`); ``cpml_thickness`` as in
+    ``make_patches_3d`` (`simulation/simulation.py:455-463`)."""
     from .fields import Fields2D
     from .particles import ParticlesBase
 
@@ -303,6 +347,8 @@ def make_patches_2d(nx, ny, dx, dy, npatch_x, npatch_y, n_guard=3, boundary_cond
             p.set_fields(Fields2D(nxp, nyp, dx, dy, p.x0, p.y0, n_guard))
             for _ in range(nspecies):
                 p.add_particles(ParticlesBase(ipatch=p.index, rank=0))
+            if cpml_thickness is not None:
+                _attach_pml_faces(p, (npatch_x, npatch_y), bc, cpml_thickness)
             patches.append(p)
     patches.init_rect_neighbor_index_2d(npatch_x, npatch_y, boundary_conditions=bc)
     patches.xmin_global, patches.xmax_global = -dx / 2, Lx - dx / 2

@@ -30,7 +30,7 @@ from . import constants
 from .collision import SimulationCollisionMixin
 from .dist import SlabComm
 from .engine import PicEngine2D
-from .patch import make_patches_2d
+from .patch import make_patches_2d, open_face_bounds
 
 
 @dataclass
@@ -510,7 +510,10 @@ class Simulation(SimulationCollisionMixin):
         self.nx_per_patch, self.ny_per_patch = nx_loc // self.npatch_x, self.ny // self.npatch_y
         self.engine = PicEngine2D(nx_loc, self.ny, self.dx, self.dy, self.n_guard, self.device, self.comm,
                                   sort_interval=self.sort_interval, boundary_conditions=self.boundary_conditions,
-                                  cpml_thickness=self.cpml_thickness)
+                                  cpml_thickness=self.cpml_thickness,
+                                  absorb_bounds=[open_face_bounds(0.0, n, d, self.cpml_thickness, npatch) for n, d, npatch in
+                                                 ((self.nx, self.dx, self.npatch_x * self.comm.size),
+                                                  (self.ny, self.dy, self.npatch_y))])
         mirrors = make_patches_2d(nx_loc, self.ny, self.dx, self.dy, self.npatch_x, self.npatch_y, self.n_guard,
                                   boundary_conditions=self.boundary_conditions, nspecies=len(self.species))
         for p in mirrors:                       # patch origins in global coordinates

@@ -18,6 +18,7 @@ from .dist import SlabComm
 from .engine3d import ATTRS3, NROWS3, SIDES3, PicEngine3D
 from .fields import FIELD_ATTRS, Fields3D, from_device_layout, to_device_layout
 from .particles import ParticlesBase
+from .patch import open_face_bounds
 from .simulation import (Callback, MPIFacade, Simulation, Species, _Facade, callback, interval_triggered,  # noqa: F401
                          load_block_device, validate_interval)          # (shared with 2-D)
 
@@ -140,7 +141,10 @@ class Simulation3D(SimulationCollisionMixin):
         self.engine = PicEngine3D(nxl, self.ny, self.nz, self.dx, self.dy, self.dz, self.n_guard, self.device,
                                   sort_interval=self.sort_interval, block_particles=self.block_particles,
                                   comm=self.comm, boundary_conditions=self.boundary_conditions,
-                                  cpml_thickness=self.cpml_thickness)
+                                  cpml_thickness=self.cpml_thickness,
+                                  absorb_bounds=[open_face_bounds(0.0, n, d, self.cpml_thickness, npatch) for n, d, npatch in
+                                                 ((self.nx, self.dx, self.npatch[0] * self.comm.size),
+                                                  (self.ny, self.dy, self.npatch[1]), (self.nz, self.dz, self.npatch[2]))])
         px, py, pz = self.npatch
         self.n_per_patch = (nxl // px, self.ny // py, self.nz // pz)
         npp, d = self.n_per_patch, (self.dx, self.dy, self.dz)

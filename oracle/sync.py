@@ -2,7 +2,8 @@
 
 numpy restatement of the reference's intra-rank patch synchronisation
 (core/patch/sync_fields2d.c, core/patch/sync_particles_2d.c), operating on the host patch mirrors.
-Checked against the reference's compiled extensions through tests/golden (G7).
+Checked against the reference's compiled extensions through tests/golden (G7; the particle sync at open, PML-shrunk
+faces through G18 in 2-D and G19 in 3-D).
 """
 from __future__ import annotations
 

@@ -780,6 +780,202 @@ def g17_sync_particles_3d_patches():
     np.savez_compressed(OUT / "g17_sync_particles_3d_patches.npz", **out)
 
 
+def load_ref_patch():
+    """core/patch/patch.py as plain Python, for the ownership bounds of its Patch2D / Patch3D (`xmin` ... `zmax` with the
+    PML shrink, :105-148) and its neighbour tables (:446-592).  On top of load_ref_cpml's stand-ins: core/boundary/utils.py
+    is loaded from where it lies; the modules the bounds never touch (particle container, species, the numba loaders of
+    core/patch/cpu.py) are empty stand-ins"""
+    RF, RC = load_ref_cpml()
+    if not hasattr(sys.modules["numba"], "typed"):
+        sys.modules["numba"].typed = None
+
+    def stand_in(name, **names):
+        m = types.ModuleType(name)
+        m.__dict__.update(names)
+        sys.modules[name] = m
+
+    stand_in("lambdapic.core.particles", ParticlesBase=object)
+    stand_in("lambdapic.core.species", Electron=object, Photon=object, Species=object)
+    stand_in("lambdapic.core.patch")
+    stand_in("lambdapic.core.patch.cpu", fill_particles_2d=None, get_num_macro_particles_2d=None, fill_particles_3d=None,
+             get_num_macro_particles_3d=None)
+    for mod, rel in (("lambdapic.core.boundary.utils", "core/boundary/utils.py"),
+                     ("lambdapic.core.patch.patch", "core/patch/patch.py")):
+        spec = importlib.util.spec_from_file_location(mod, REF / rel)
+        m = importlib.util.module_from_spec(spec)
+        sys.modules[mod] = m
+        spec.loader.exec_module(m)
+    return RF, RC, m
+
+
+def _sync_particles_open(dim, npp, npatch, d, th, bc, rng):
+    """one Patches.sync_particles (`core/patch/patch.py:705-763`) of the reference's compiled extension on a patch grid with
+    open (PML) faces.  The patches handed to the extension are the REFERENCE's Patch2D / Patch3D with its PML objects
+    attached, so `xmin` ... `zmax` are its own properties; the particle bags are the mirror's.  Returns the fixture entries."""
+    from lambdapic_amd.patch import OFFSET_2D, OFFSET_3D, Boundary2D, Boundary3D, make_patches_3d
+    RF, RC, RP = load_ref_patch()
+    axes = "xyz"[:dim]
+    B, OFF = (Boundary2D, OFFSET_2D) if dim == 2 else (Boundary3D, OFFSET_3D)
+    nb = len(B)
+    n = tuple(a * b for a, b in zip(npp, npatch))
+    L = [a * b for a, b in zip(n, d)]                                   # simulation.py:221-222, :1290-1292
+    M = make_patches_2d(*n, *d, *npatch, 3, boundary_conditions=bc) if dim == 2 else \
+        make_patches_3d(n, d, npatch, 3, boundary_conditions=bc)
+    pml_cls = dict(xmin=RC.PMLXmin, xmax=RC.PMLXmax, ymin=RC.PMLYmin, ymax=RC.PMLYmax, zmin=RC.PMLZmin, zmax=RC.PMLZmax)
+    R = RP.Patches(dim)
+    for m in M:
+        ip = tuple(getattr(m, "ipatch_" + a) for a in axes)
+        org = [i * l / k for i, l, k in zip(ip, L, npatch)]              # simulation.py:482-483, :1397
+        p = (RP.Patch2D if dim == 2 else RP.Patch3D)(0, m.index, *ip, *org, *npp, *d)
+        p.set_fields((RF.Fields2D if dim == 2 else RF.Fields3D)(*npp, *d, *org, 3))
+        for a, i, k in zip(axes, ip, npatch):                            # simulation.py:455-463
+            if bc[a + "min"] == "pml" and i == 0:
+                p.add_pml_boundary(pml_cls[a + "min"](p.fields, thickness=th))
+            if bc[a + "max"] == "pml" and i == k - 1:
+                p.add_pml_boundary(pml_cls[a + "max"](p.fields, thickness=th))
+        p.add_particles(m.particles[0])
+        R.append(p)
+    if dim == 2:
+        R.init_rect_neighbor_index_2d(*npatch, boundary_conditions=bc)
+    else:
+        R.init_rect_neighbor_index_3d(*npatch, boundary_conditions=bc)
+    for p, m in zip(R, M):
+        p.neighbor_ipatch[:] = p.neighbor_index                         # one rank: the local index is the global one
+        assert np.array_equal(p.neighbor_ipatch, m.neighbor_ipatch)
+    for a, dd, l in zip(axes, d, L):                                     # simulation.py:427-430, :1321-1326
+        setattr(R, a + "min_global", -dd / 2)
+        setattr(R, a + "max_global", l - dd / 2)
+    npat = len(M)
+    # the bounds the extension tests against: the patch's property, widened by half a cell (sync_particles_2d.c:236-241)
+    lo = np.array([[getattr(p, a + "min") - 0.5 * dd for a, dd in zip(axes, d)] for p in R])
+    hi = np.array([[getattr(p, a + "max") + 0.5 * dd for a, dd in zip(axes, d)] for p in R])
+    for k, p in enumerate(R):            # the shrink is there, and only at the open faces
+        for c, (a, dd) in enumerate(zip(axes, d)):
+            ip, last = getattr(p, "ipatch_" + a), npatch[c] - 1
+            assert (lo[k, c] > getattr(p, a + "0")) == (bc[a + "min"] == "pml" and ip == 0)
+            assert (hi[k, c] < getattr(p, a + "0") + (npp[c] - 1) * dd) == (bc[a + "max"] == "pml" and ip == last)
+    names = list(axes) + ["ux", "w", "_id", "is_dead"]
+    out = dict(neighbor_ipatch=np.stack([p.neighbor_ipatch for p in R]), lo=lo, hi=hi,
+               origin=np.array([[getattr(p, a + "0") for a in axes] for p in R]))
+    leavers, probes = [], []             # (patch, slot, class) / (patch, slot, axis, upper?, which: 0 on, 1 inside, 2 outside)
+    for k, p in enumerate(R):
+        q = p.particles[0]
+        npart = (240 + 7 * k) if dim == 2 else (180 + 5 * k)
+        q.initialize(npart)
+        org = [getattr(p, a + "0") for a in axes]
+        for a, o, n_ax, dd in zip(axes, org, npp, d):
+            getattr(q, a)[:] = o + (rng.uniform(-0.5, n_ax - 0.5, npart) + rng.uniform(-0.95, 0.95, npart)) * dd
+        q.ux[:] = rng.integers(-128, 129, npart) / 64.0          # (short bit patterns: the fixture stays small)
+        q.w[:] = 1 + rng.integers(0, 65, npart) / 64.0
+        q.is_dead[k % 5::11] = True
+        slots = list(rng.permutation(npart))
+        # particles that sit inside the layer of every open face of this patch and have not moved
+        for c, (a, dd) in enumerate(zip(axes, d)):
+            for upper, has in ((False, lo[k, c] > org[c]), (True, hi[k, c] < org[c] + (npp[c] - 1) * dd)):
+                if not has:
+                    continue
+                for _ in range(6):
+                    s = slots.pop()
+                    for c2, (a2, n2, d2) in enumerate(zip(axes, npp, d)):
+                        getattr(q, a2)[s] = org[c2] + rng.uniform(-0.5, n2 - 0.5) * d2
+                    cell = rng.uniform(-0.5, th - 0.6)
+                    getattr(q, a)[s] = org[c] + ((npp[c] - 1 - cell) if upper else cell) * dd
+                    q.is_dead[s] = False
+        # one sure leaver per boundary class
+        for b in B:
+            s = slots.pop()
+            for c, (a, off, n_ax, dd) in enumerate(zip(axes, OFF[b], npp, d)):
+                getattr(q, a)[s] = org[c] + {-1: -0.8, 0: 0.5 * (n_ax - 1), 1: n_ax - 0.2}[off] * dd
+            q.is_dead[s] = False
+            leavers.append((k, s, int(b)))
+        # every face: on the widened bound, one ulp inside, one ulp outside (the other coordinates mid-patch)
+        for c, a in enumerate(axes):
+            for upper in (False, True):
+                bound = hi[k, c] if upper else lo[k, c]
+                inward = -np.inf if upper else np.inf
+                for which, v in enumerate((bound, np.nextafter(bound, inward), np.nextafter(bound, -inward))):
+                    s = slots.pop()
+                    for c2, (a2, n2, d2) in enumerate(zip(axes, npp, d)):
+                        getattr(q, a2)[s] = org[c2] + 0.5 * (n2 - 1) * d2
+                    getattr(q, a)[s] = v
+                    q.is_dead[s] = False
+                    probes.append((k, s, c, upper, which))
+        out.update(snap(q, names, f"pin{k}_"))
+    parts = [p.particles[0] for p in R]
+    mod = oracle.ref_module("patch", f"sync_particles_{dim}d")
+    count, fill = getattr(mod, f"get_npart_to_extend_{dim}d"), getattr(mod, f"fill_particles_from_boundary_{dim}d")
+    ext, inc, outg, alive = count(parts, list(R), npat, *d)
+    out.update(npart_to_extend=np.asarray(ext).copy(), npart_incoming=np.asarray(inc).copy(),
+               npart_outgoing=np.asarray(outg).copy(), npart_alive=np.asarray(alive).copy())
+    for q, k in zip(parts, ext):
+        if k > 0:
+            q.extend(int(k))
+    fill(parts, list(R), inc, outg, npat, *d, *[getattr(R, a + s) for a in axes for s in ("min_global", "max_global")],
+         parts[0].attrs)
+    for k, q in enumerate(parts):
+        out.update(snap(q, names, f"pout{k}_"))
+    # ---- coverage
+    live_at = {}                                                        # id -> (patch, slot) of every live particle afterwards
+    for k, q in enumerate(parts):
+        for s in np.flatnonzero(~q.is_dead):
+            assert int(q.id[s]) not in live_at
+            live_at[int(q.id[s])] = (k, int(s))
+    ident = lambda k, s: int(out[f"pin{k}__id"].view(np.uint64)[s])
+    outg2 = out["npart_outgoing"].reshape(npat, nb)
+    assert outg2.min() > 0                                               # every class of every patch has a leaver
+    mixed = 0
+    for k, s, b in leavers:
+        to = int(out["neighbor_ipatch"][k, b])
+        if to >= 0:                                                      # a neighbour: the leaver migrates
+            assert live_at[ident(k, s)][0] == to and (to != k or live_at[ident(k, s)][1] != s), (k, b)
+        else:                                                            # none: it dies where it is, position blanked
+            assert ident(k, s) not in live_at and parts[k].is_dead[s] and np.isnan(parts[k].x[s]), (k, b)
+            faces = [B[a.upper() + ("MIN" if o < 0 else "MAX")] for a, o in zip(axes, OFF[B(b)]) if o]
+            beyond = [int(out["neighbor_ipatch"][k, int(f)]) >= 0 for f in faces]
+            mixed += any(beyond) and not all(beyond)
+    assert mixed > 0                     # through an interior (or periodic) face on one axis and an open face on another
+    seam_lost = 0
+    for k, s, c, upper, which in probes:
+        face = B[axes[c].upper() + ("MAX" if upper else "MIN")]
+        open_face = out["neighbor_ipatch"][k, int(face)] < 0
+        alive_now = ident(k, s) in live_at
+        if which < 2:                                                    # on the bound / inside: stays, slot untouched
+            assert live_at[ident(k, s)] == (k, s), (k, c, upper, which)
+        elif open_face:                                                  # one ulp outside an open face: absorbed
+            assert not alive_now and np.isnan(getattr(parts[k], axes[c])[s]), (k, c, upper)
+        else:
+            seam_lost += not alive_now
+    out["seam_lost"] = seam_lost
+    return out
+
+
+def _open_fixture(dim, name, npp, npatch, d, th, mixes, seed):
+    rng = np.random.default_rng(seed)
+    out = dict(npp=np.array(npp), npatch=np.array(npatch), d=np.array(d), thickness=th, mixes=np.array(list(mixes)))
+    for tag, periodic in mixes.items():
+        bc = {a + s: ("periodic" if a in periodic else "pml") for a in "xyz"[:dim] for s in ("min", "max")}
+        out[tag + "_periodic"] = np.array([a in periodic for a in "xyz"[:dim]])
+        out.update({f"{tag}_{k}": v for k, v in _sync_particles_open(dim, npp, npatch, d, th, bc, rng).items()})
+    np.savez_compressed(OUT / name, **out)
+
+
+def g18_sync_particles_open_2d():
+    """2-D particle ownership at OPEN faces: 3 x 2 patches of 32 x 20 cells, PML of 6 cells, (a) on all four faces, (b) on
+    the x faces with y periodic.  `get_npart_to_extend_2d` + `fill_particles_from_boundary_2d`
+    (`core/patch/sync_particles_2d.c:204-518`) on the reference's own Patch2D bounds (`core/patch/patch.py:105-134`):
+    leavers without a neighbour die in place, everything outside the pulled-in, half-cell-widened bounds is killed and
+    blanked (:185-202).  dx = 5e-8 with 96 cells over 3 patches is a case where x0 + (nx_total - 1 - t) dx differs from
+    the reference's (x0_patch + (nx_patch - 1) dx) - t dx by one ulp."""
+    _open_fixture(2, "g18_sync_particles_open_2d.npz", (32, 20), (3, 2), (5e-8, 4e-8), 6, {"a": "", "b": "y"}, SEED + 18)
+
+
+def g19_sync_particles_open_3d():
+    """the 3-D twin (`core/patch/sync_particles_3d.c`, `core/patch/patch.py:136-148`): 2 x 2 x 2 patches of 8 x 8 x 9 cells,
+    three different spacings, PML of 3 cells, (a) on all six faces, (b) on the x and z faces with y periodic"""
+    _open_fixture(3, "g19_sync_particles_open_3d.npz", (8, 8, 9), (2, 2, 2), (1.0e-7, 1.5e-7, 0.8e-7), 3,
+                  {"a": "", "b": "y"}, SEED + 19)
+
+
 def g15_sort_variants():
     """the branches of the reference's sort that g6 does not take, recorded from its compiled extensions:
     (a) sort_particles_patches_3d (core/sort/cpu3d.c) on a 6 x 5 x 4 bucket grid with dead slots and out-of-range
@@ -839,6 +1035,10 @@ def main():
         g16_sync_fields_3d_patches()
         g17_sync_particles_3d_patches()
         sys.exit(0)
+    if "--only-g18" in sys.argv:
+        g18_sync_particles_open_2d()
+        g19_sync_particles_open_3d()
+        return
     if "--only-g14" in sys.argv:
         g14_sync_particles_3d()
         return
@@ -871,6 +1071,8 @@ def main():
     g16_sync_fields_3d_patches()
     g17_sync_particles_3d_patches()
     g15_sort_variants()
+    g18_sync_particles_open_2d()
+    g19_sync_particles_open_3d()
     for f in sorted(OUT.glob("*.npz")):
         print(f.name, f.stat().st_size)
 

@@ -42,6 +42,46 @@ def particles_from(g, prefix, names=None):
     return p
 
 
+OPEN_FIXTURES = {2: "g18_sync_particles_open_2d", 3: "g19_sync_particles_open_3d"}
+OPEN_CASES = [(dim, mix) for dim in (2, 3) for mix in "ab"]
+
+
+def open_patches(g, mix, load=True):
+    """mirror patches of one boundary mix of g18 (2-D) / g19 (3-D) with their PML faces attached and, with ``load``,
+    the recorded input particles; -> (patches, spacings, boundary conditions)"""
+    from lambdapic_amd.patch import make_patches_2d, make_patches_3d
+    npp, npatch = tuple(int(v) for v in g["npp"]), tuple(int(v) for v in g["npatch"])
+    d, th, dim = tuple(float(v) for v in g["d"]), int(g["thickness"]), len(npp)
+    axes = "xyz"[:dim]
+    bc = {a + s: ("periodic" if per else "pml") for a, per in zip(axes, g[mix + "_periodic"]) for s in ("min", "max")}
+    n = tuple(a * b for a, b in zip(npp, npatch))
+    P = make_patches_2d(*n, *d, *npatch, 3, boundary_conditions=bc, cpml_thickness=th) if dim == 2 else \
+        make_patches_3d(n, d, npatch, 3, boundary_conditions=bc, cpml_thickness=th)
+    assert np.array_equal(np.stack([p.neighbor_ipatch for p in P]), g[mix + "_neighbor_ipatch"])
+    if load:
+        for k, p in enumerate(P):
+            q = p.particles[0]
+            q.initialize(g[f"{mix}_pin{k}_x"].size)
+            for a in list(axes) + ["ux", "w", "_id", "is_dead"]:
+                getattr(q, a)[:] = g[f"{mix}_pin{k}_{a}"]
+    return P, d, bc
+
+
+def check_open_out(g, mix, P):
+    """the particle bags after one sync == the reference's, slot for slot and bit for bit: is_dead, every attribute of
+    the live slots, and NaN exactly where the reference has NaN"""
+    axes = "xyz"[: len(g["npp"])]
+    for k, p in enumerate(P):
+        q = p.particles[0]
+        assert q.npart == g[f"{mix}_pout{k}_x"].size, k
+        assert np.array_equal(q.is_dead, g[f"{mix}_pout{k}_is_dead"]), k
+        live = ~q.is_dead
+        for a in list(axes) + ["ux", "w", "_id"]:
+            assert np.array_equal(getattr(q, a)[live].view(np.uint64), g[f"{mix}_pout{k}_{a}"][live].view(np.uint64)), (k, a)
+        for a in axes:
+            assert np.array_equal(np.isnan(getattr(q, a)), np.isnan(g[f"{mix}_pout{k}_{a}"])), (k, a)
+
+
 def assert_close(actual, expected, rtol, scale=None, what=""):
     """|a-e| <= rtol * scale, scale defaulting to max|e|; NaN patterns must coincide."""
     a, e = np.asarray(actual, dtype=np.float64), np.asarray(expected, dtype=np.float64)

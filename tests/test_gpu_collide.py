@@ -6,6 +6,10 @@ PARTICLE's own |u| after the collisions rather than to its pair's |p|: a particl
 pair's, so this asks more (for an electron paired with an ion ~1836 times more).  Measured (float64 against longdouble,
 every pair on the same branch in both; the p_perp <= 1e-10 p branch does not occur) and what the kernel gave:
     intra  2-D 2.7e-14, 3-D 3.8e-14, kernel 1.6 / 2.2e-14;   inter  2-D 1.1 .. 1.5e-13, 3-D 1.4 .. 2.6e-13, kernel 1.7 .. 2.2e-13
+Stores shaped by absorption (test_collide_on_a_store_shaped_by_absorption; the launches of one collide() chained), reference
+float64 against longdouble and what the kernel gave, 2-D / 3-D:
+    dead     5.3e-14 / 2.8e-14, kernel 9.2e-14 / 2.3e-14;     partial  2.3e-14 / 3.4e-14, kernel 2.5e-14 / 3.7e-14
+    large    8.6e-14 / 8.4e-14, kernel 8.9e-14 / 1.1e-13;     pairs    2.0e-14 / 2.6e-14, kernel 7.1e-14 / 3.2e-14
 """
 import functools
 
@@ -39,22 +43,22 @@ def u01(lo, hi):
 def relerr(u, w):
     return float(np.max(np.linalg.norm((u - w).astype(float), axis=1) / np.maximum(np.linalg.norm(w.astype(float), axis=1), 1e-300)))
 
-def cells_of(sp, dim):
-    shape = SHAPE[dim]
+def cells_of(sp, dim, shape=None):
+    shape = shape or SHAPE[dim]
     idx = [np.clip(np.floor(sp[a] / DX + 0.5).astype(int), 0, n - 1) for a, n in zip("xyz", shape)]
     return np.ravel_multi_index(idx, shape)
 
-def reference(dim, a, b, lnl, pidx, T, debye_extra=()):
+def reference(dim, a, b, lnl, pidx, T, debye_extra=(), shape=None):
     """momenta [n][3] of a (and b) after one lpa_collide, computed in number type T; + the branch every pair took"""
     inter = b is not None
     sides = [a, b] if inter else [a]
     u = [np.stack([s["ux"], s["uy"], s["uz"]], 1).astype(T) for s in sides]
-    cells = [cells_of(s, dim) for s in sides]
+    cells = [cells_of(s, dim, shape) for s in sides]
     vol, c, one = T(DX) ** dim, T(C), T(1)
-    inv_d2 = np.zeros(int(np.prod(SHAPE[dim])), T)
+    inv_d2 = np.zeros(int(np.prod(shape or SHAPE[dim])), T)
     if lnl <= 0:                         # debye_length_patches + constrain_debye_length_patches over the species passed
         ntot = np.zeros_like(inv_d2)
-        extra = [(e, cells_of(e, dim), np.stack([e["ux"], e["uy"], e["uz"]], 1).astype(T)) for e in debye_extra]
+        extra = [(e, cells_of(e, dim, shape), np.stack([e["ux"], e["uy"], e["uz"]], 1).astype(T)) for e in debye_extra]
         for s, cl, us in list(zip(sides, cells, u)) + extra:
             for g in np.unique(cl):
                 k = cl == g
@@ -146,13 +150,18 @@ def reference(dim, a, b, lnl, pidx, T, debye_extra=()):
 
 def make_species(dim, counts, q, m, rng, stride, wscale):
     """cell g (every ``stride``-th cell) holds counts[k-th populated cell mod len] particles off the cell boundaries"""
-    shape = SHAPE[dim]
-    cell = np.repeat(np.arange(0, int(np.prod(shape)), stride), [counts[k % len(counts)] for k in range(len(range(0, int(np.prod(shape)), stride)))])
+    cells = np.arange(0, int(np.prod(SHAPE[dim])), stride)
+    return make_cells(dim, SHAPE[dim], cells, [counts[k % len(counts)] for k in range(len(cells))], q, m, rng, wscale)
+
+def make_cells(dim, shape, cells, counts, q, m, rng, wscale):
+    """the k-th of ``cells`` (flat indices into ``shape``) holds counts[k] particles off the cell boundaries; the thermal
+    spread cycles over three decades, the first four populated cells are exactly at rest"""
+    cell, ordinal = np.repeat(cells, counts), np.repeat(np.arange(len(cells)), counts)
     n = len(cell)
     pos = (np.stack(np.unravel_index(cell, shape), 1) + rng.uniform(-0.45, 0.45, (n, dim))) * DX
-    sigma = np.array([0.01, 0.3, 3.0])[(cell // stride) % 3]
+    sigma = np.array([0.01, 0.3, 3.0])[ordinal % 3]
     uu = rng.normal(size=(n, 3)) * sigma[:, None] + np.array([0.5, 0.0, -0.2]) * sigma[:, None]
-    uu[cell < 4 * stride] = 0.0                   # the first populated cells: pairs exactly at rest
+    uu[ordinal < 4] = 0.0                         # the first populated cells: pairs exactly at rest
     sp = {"q": q, "m": m, "w": DX ** dim * (wscale * rng.uniform(0.5, 2.0, n) if wscale else np.full(n, 1e29)),
           "id": rng.permutation(n).astype(np.uint64) + np.uint64(5 << 50), "ux": uu[:, 0], "uy": uu[:, 1], "uz": uu[:, 2]}
     sp.update({a: pos[:, k] for k, a in enumerate("xyz"[:dim])})
@@ -177,12 +186,12 @@ def load(eng, dim, sp, perm=None):
     s.n, s.n_sorted, s.tiling = n, 0, None
     return i
 
-def engine(dim, order):
+def engine(dim, order, shape=None):
     from lambdapic_amd.engine import PicEngine2D
     from lambdapic_amd.engine3d import PicEngine3D
     if dim == 2:
-        return PicEngine2D(*SHAPE[2], DX, DX, order=order)
-    eng = PicEngine3D(*SHAPE[3], DX, DX, DX)
+        return PicEngine2D(*(shape or SHAPE[2]), DX, DX, order=order)
+    eng = PicEngine3D(*(shape or SHAPE[3]), DX, DX, DX)
     eng.order = order
     return eng
 
@@ -350,3 +359,120 @@ def test_simulation3d_staged_step_collides():
     assert seen == list(range(5))
     assert staged.engine._coll_launches == DUE == fused.engine._coll_launches
     assert _close(_momenta(staged, 3), _momenta(fused, 3), 1e-9)
+
+# ---- stores that absorption has shaped: dead slots, grids ending in partial tiles, deep cells, pair_index > 0 -----------------
+# Grids that are no multiple of the 8 x 32 / 4 x 4 x 16 tiles; the populated cells include the last, partial tile along every axis.
+SHAPE_P = {2: (12, 40), 3: (6, 6, 20)}
+CELLS_P = {2: [(0, 0), (3, 5), (7, 31), (8, 0), (11, 10), (5, 32), (2, 39), (9, 33), (11, 39), (8, 32), (10, 38), (4, 17)],
+           3: [(0, 0, 0), (3, 3, 15), (4, 0, 0), (5, 2, 7), (0, 4, 3), (2, 5, 9), (1, 1, 16), (3, 2, 19), (4, 4, 16), (5, 5, 19),
+               (4, 5, 17), (0, 5, 18)]}
+COUNTS_PA, COUNTS_PB = (2, 3, 5, 8, 1, 64, 7, 65, 9, 4, 33, 2), (1, 2, 7, 3, 4, 9, 0, 5, 66, 2, 1, 6)
+BIG = 300           # one cell deeper than the 256 the LDS path holds: global-memory pairing, sort_mem at P = 512
+
+def _sub(sp, keep):
+    return {k: (v[keep] if isinstance(v, np.ndarray) else v) for k, v in sp.items()}
+
+def _with_u(sp, u):
+    return dict(sp, ux=u[:, 0], uy=u[:, 1], uz=u[:, 2])
+
+@functools.lru_cache(maxsize=None)
+def shaped_data(dim, case):
+    """(a, b, dead ids of a / of b, launches [(side a, side b or None, lnLambda, pair index)], expected momenta per species
+    in float64 chained over the launches, tolerance, branches) -- all of it computed on the CPU.  Every launch list is what
+    ONE engine.collide() does for the groups of the case, in its launch order."""
+    rng = np.random.default_rng(1000 * dim + {"dead": 1, "partial": 2, "large": 3, "pairs": 4}[case])
+    shape = SHAPE_P[dim]
+    cells = [int(np.ravel_multi_index(c, shape)) for c in CELLS_P[dim]]
+    ca, cb = list(COUNTS_PA), list(COUNTS_PB)
+    if case == "large":                                # cell 5: 300 electrons (intra) and 300 + 5 (inter: rep = 60, rem = 0);
+        ca[5], cb[5] = BIG, 5                          # cell 8: 7 + 300 the other way round (rep = 42, rem = 6)
+        ca[8], cb[8] = 7, BIG
+    a = make_cells(dim, shape, cells, ca, QE, ME, rng, 1e29)
+    b = make_cells(dim, shape, cells, cb, -QE, MI, rng, 3e28)
+    dead = [np.zeros(0, np.uint64), np.zeros(0, np.uint64)]
+    if case == "dead":                                 # ~10 % of each species, scattered: most populated cells lose some
+        dead = [np.sort(rng.choice(s["id"], size=len(s["id"]) // 10, replace=False)) for s in (a, b)]
+    launches = {"dead": [(0, 0, 10.0, 0), (0, 1, 10.0, 1)], "partial": [(0, 1, 0.0, 0)],
+                "large": [(0, 0, 10.0, 0), (0, 1, 10.0, 1)], "pairs": [(0, 0, 10.0, 0), (0, 1, 10.0, 1), (1, 1, 10.0, 2)]}[case]
+    out, err, branches = {}, 0.0, {}
+    for T in (np.float64, np.longdouble):
+        live = [_sub(s, ~np.isin(s["id"], d)) for s, d in zip((a, b), dead)]
+        branches[T] = []
+        for sa, sb, lnl, pidx in launches:
+            u, br = reference(dim, live[sa], live[sb] if sb != sa else None, lnl, pidx, T, shape=shape)
+            live[sa] = _with_u(live[sa], u[0])
+            if sb != sa:
+                live[sb] = _with_u(live[sb], u[1])
+            branches[T].append(br)
+        out[T] = [np.stack([s["ux"], s["uy"], s["uz"]], 1) for s in live]
+    assert branches[np.float64] == branches[np.longdouble], "float64 and longdouble took different branches: pick another seed"
+    err = max(relerr(x, y) for x, y in zip(out[np.float64], out[np.longdouble]))
+    ids = [s["id"][~np.isin(s["id"], d)] for s, d in zip((a, b), dead)]
+    return a, b, dead, launches, out[np.float64], ids, max(10 * err, 1e-13), err, branches[np.float64]
+
+def _kill(eng, dim, i, ids):
+    """blank the positions of the particles ``ids`` in the SORTED store ``i``, as the push does to a particle it absorbs;
+    -> (slot mask, what those slots hold besides the position)"""
+    want = torch.from_numpy(ids.view(np.int64)).to(eng.device)
+    if dim == 2:
+        sp = eng.species[i]
+        mask = torch.isin(sp.cset.id[: sp.n], want)
+        for a in "xy":
+            sp.cset.arr(a)[: sp.n][mask] = float("nan")
+        rest = lambda: torch.stack([sp.cset.arr(a)[: sp.n][mask] for a in ("ux", "uy", "uz", "w")] +
+                                   [sp.cset.id[: sp.n][mask].view(torch.float64)])
+        pos = lambda: torch.stack([sp.cset.arr(a)[: sp.n][mask] for a in "xy"])
+    else:
+        sp = eng.species[i]
+        data = sp["data"][:, : sp["n"]]
+        mask = torch.isin(data[8].view(torch.int64), want)
+        data[:3, mask] = float("nan")
+        rest = lambda: torch.stack([data[k][mask] for k in (3, 4, 5, 7, 8)])
+        pos = lambda: data[:3][:, mask]
+    assert int(mask.sum().item()) == len(ids)
+    return rest, pos, rest().clone()
+
+@pytest.mark.parametrize("case", ["dead", "partial", "large", "pairs"])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_collide_on_a_store_shaped_by_absorption(dim, case):
+    """lpa_collide on what a run with open faces hands it, against the same contract restatement and with the same
+    tolerance rule as above (ten times the float64 / longdouble discrepancy of the reference on THESE inputs, floor 1e-13):
+      dead     ~10 % of the slots of both sorted stores are dead the way the push leaves an absorbed particle (position
+               NaN), some inside populated cells: the reference pairs the others, the dead slots come back untouched;
+      partial  grids of 12 x 40 / 6 x 6 x 20 cells, populated cells in the last partial tile along every axis, varying lnLambda;
+      large    a cell of 300 electrons (intra-species) and cells of 300 + 5 and 7 + 300 (inter-species): the global-memory
+               pairing, the sort at P = 512 and weight corrections with quotients of 60 and 42 (remainder 6);
+      pairs    groups [[e, e, i], [i, i]] in one collide(): pair_index 0, 1, 2 in launch order, each launch working on
+               what the one before left."""
+    a, b, dead, launches, want, ids, tol, err, branches = shaped_data(dim, case)
+    shape = SHAPE_P[dim]
+    eng = engine(dim, _lib.LPA_ORDER_STRIPED, shape)
+    ia, ib = load(eng, dim, a), load(eng, dim, b)
+    groups = {"dead": [[ia, ia, ib]], "partial": [[ia, ib]], "large": [[ia, ia, ib]], "pairs": [[ia, ia, ib], [ib, ib]]}[case]
+    eng.add_collision(groups, lnLambda=launches[0][2], seed=SEED)
+    eng.collision["itime"], eng._coll_launches = ITIME, []
+    kept = []
+    if case == "dead":                                   # sort as a due step does (look-ahead 0), then absorb
+        eng._coll_sorting = True
+        eng.sort(ia), eng.sort(ib)
+        eng._coll_sorting = False
+        kept = [_kill(eng, dim, i, d) for i, d in ((ia, dead[0]), (ib, dead[1]))]
+    eng.collide(DT)
+    eng.check_collision()
+    assert eng._coll_launches == [(ITIME, (ia, ib)[sa], (ia, ib)[sb]) for sa, sb, _, _ in launches]
+    assert [eng.collision["pairs"].index((x, y)) for _, x, y in eng._coll_launches] == [l[3] for l in launches]
+    worst = 0.0
+    for sp, i, w, live_ids in zip((a, b), (ia, ib), want, ids):
+        got = by_id(eng, dim, i)
+        o = np.argsort(live_ids)
+        assert np.array_equal(got["_id"].view(np.uint64), live_ids[o])
+        sel = np.flatnonzero(np.isin(sp["id"], live_ids))[o]
+        for attr in ("x", "y", "z")[: dim] + ("w",):
+            assert np.array_equal(got[attr], sp[attr][sel]), attr
+        worst = max(worst, relerr(np.stack([got["ux"], got["uy"], got["uz"]], 1), w[o]))
+    for rest, pos, before in kept:                       # dead slots: still dead, nothing else touched
+        assert torch.isnan(pos()).all() and torch.equal(rest().view(torch.int64), before.view(torch.int64))
+    kinds = {br[2] for launch in branches for br in launch}
+    assert True in kinds and (False in kinds or case == "partial")      # both scattering-angle branches occur
+    print(f"shaped dim {dim} {case}: reference f64 / longdouble {err:.3e} worst {worst:.3e} tolerance {tol:.3e}")
+    assert worst < tol

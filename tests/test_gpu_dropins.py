@@ -5,7 +5,7 @@ plus the resident engine's TILE sort pinned to g6's bucket histogram and particl
 import numpy as np
 import pytest
 
-from helpers import assert_close, particles_from
+from helpers import OPEN_CASES, OPEN_FIXTURES, assert_close, check_open_out, open_patches, particles_from
 from lambdapic_amd import kernels
 from lambdapic_amd.patch import make_patches_2d
 
@@ -375,3 +375,31 @@ def test_sync_particles_3d_dropins_vs_reference_golden(golden):
             assert np.array_equal(getattr(q, a)[live].view(np.uint64), g[f"pout{k}_{a}"][live].view(np.uint64)), (k, a)
         for a in "xyz":
             assert np.isnan(getattr(q, a)[~live]).all(), (k, a)
+
+
+# ---- open (PML) faces: g18 (2-D, 3 x 2 patches) and g19 (3-D, 2 x 2 x 2), two boundary mixes each ---------------------
+@pytest.mark.parametrize("dim,mix", OPEN_CASES)
+def test_sync_particles_dropins_open_faces_vs_reference_golden(golden, dim, mix):
+    """`get_npart_to_extend_2d/3d` + `fill_particles_from_boundary_2d/3d` with `neighbor_ipatch == -1` on the reference's
+    fixtures: patches whose bounds are pulled in by a PML, leavers through every boundary class (those without a neighbour
+    die in place, among them the ones that cross an interior face on one axis and an open face on another), particles on,
+    one ulp inside and one ulp outside every bound.  The four count arrays, the slot every incoming particle lands in, the
+    is_dead flags, the NaN pattern and every attribute are the reference's, bit for bit."""
+    g = golden(OPEN_FIXTURES[dim])
+    P, d, _ = open_patches(g, mix)
+    axes = "xyz"[:dim]
+    lo = np.array([[getattr(p, a + "min") - 0.5 * dd for a, dd in zip(axes, d)] for p in P])
+    hi = np.array([[getattr(p, a + "max") + 0.5 * dd for a, dd in zip(axes, d)] for p in P])
+    assert np.array_equal(lo, g[mix + "_lo"]) and np.array_equal(hi, g[mix + "_hi"])       # the bounds the kernels get
+    parts, npat = [p.particles[0] for p in P], len(P)
+    count = kernels.get_npart_to_extend_2d if dim == 2 else kernels.get_npart_to_extend_3d
+    fill = kernels.fill_particles_from_boundary_2d if dim == 2 else kernels.fill_particles_from_boundary_3d
+    ext, inc, outg, alive = count(parts, list(P), npat, *d)
+    for got, key in ((ext, "npart_to_extend"), (inc, "npart_incoming"), (outg, "npart_outgoing"), (alive, "npart_alive")):
+        assert np.array_equal(np.asarray(got).ravel(), g[f"{mix}_{key}"].ravel()), key
+    for q, n in zip(parts, ext):                       # Patches.sync_particles, core/patch/patch.py:705-763
+        if n > 0:
+            q.extend(int(n))
+    fill(parts, list(P), inc, outg, npat, *d, *[getattr(P, a + s) for a in axes for s in ("min_global", "max_global")],
+         parts[0].attrs)
+    check_open_out(g, mix, P)

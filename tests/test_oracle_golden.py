@@ -12,7 +12,8 @@ import pytest
 
 import oracle
 from oracle import driver, sync
-from helpers import (PATTRS, PEB, assert_close, fields2d_from, fields3d_from, particles_from)
+from helpers import (OPEN_CASES, OPEN_FIXTURES, PATTRS, PEB, assert_close, check_open_out, fields2d_from, fields3d_from,
+                     open_patches, particles_from)
 from lambdapic_amd.patch import make_patches_2d
 
 
@@ -431,3 +432,39 @@ def test_g17_sync_particles_3d_patch_list(golden):
     assert np.array_equal(alive, g["npart_alive"])
     _check_g17_out(g, P)
     assert int(g["npart_outgoing"].reshape(8, 26).sum(0).min()) > 0              # all 26 classes move particles
+
+
+# ---- particle ownership at OPEN (PML) faces: g18 (2-D, 3 x 2 patches) / g19 (3-D, 2 x 2 x 2), two boundary mixes each ----
+@pytest.mark.parametrize("dim,mix", OPEN_CASES)
+def test_open_face_patch_bounds(golden, dim, mix):
+    """the mirror's ownership bounds (`lambdapic_amd/patch.py`: origin, node n - 1, PML shrink) are the reference's
+    `Patch2D` / `Patch3D` properties (`core/patch/patch.py:105-148`), recorded half-cell-widened: exactly"""
+    g = golden(OPEN_FIXTURES[dim])
+    P, d, bc = open_patches(g, mix, load=False)
+    axes = "xyz"[:dim]
+    assert np.array_equal(np.array([[getattr(p, a + "0") for a in axes] for p in P]), g[mix + "_origin"])
+    lo = np.array([[getattr(p, a + "min") - 0.5 * dd for a, dd in zip(axes, d)] for p in P])
+    hi = np.array([[getattr(p, a + "max") + 0.5 * dd for a, dd in zip(axes, d)] for p in P])
+    assert np.array_equal(lo, g[mix + "_lo"]) and np.array_equal(hi, g[mix + "_hi"])
+    shrunk = int((lo > g[mix + "_origin"]).sum())          # the lower bound lies above node 0 only where a layer is
+    assert shrunk == sum(int(np.prod(g["npatch"])) // int(g["npatch"][c]) for c, a in enumerate(axes) if bc[a + "min"] == "pml")
+    # without PML objects attached the bounds are the plain ones
+    Q = open_patches(g, mix, load=False)[0]
+    for q in Q:
+        q.pml_boundary.clear()
+        assert all(getattr(q, a + "min") == getattr(q, a + "0") for a in axes)
+
+
+@pytest.mark.parametrize("dim,mix", OPEN_CASES)
+def test_open_face_sync_particles(golden, dim, mix):
+    """the oracle's sync_particles_2d / _3d against the reference's compiled extension at open faces
+    (`core/patch/sync_particles_2d.c:185-202,204-518` and the 3-D twin): a leaver without a neighbour dies in place, whatever
+    lies outside the pulled-in bounds is killed and blanked, a particle ON the bound stays -- the four count arrays,
+    the flags, the NaN pattern and every attribute, bit for bit"""
+    g = golden(OPEN_FIXTURES[dim])
+    P, d, _ = open_patches(g, mix)
+    alive = sync.sync_particles_2d(P, 0, *d) if dim == 2 else sync.sync_particles_3d(P, 0, d)
+    assert np.array_equal(alive, g[mix + "_npart_alive"])
+    check_open_out(g, mix, P)
+    assert int(g[mix + "_npart_outgoing"].min()) > 0       # every class of every patch has a leaver
+    assert int((g[mix + "_neighbor_ipatch"] < 0).sum()) > 0
