@@ -826,6 +826,57 @@ int lpa_collide(const lpa_grid *g, const lpa_particles *pa, const lpa_tiling *ta
                 const lpa_particles *pb, const lpa_tiling *tb, double qb, double mb, const lpa_collide_params *cp,
                 void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- nonlinear Compton photon emission, LCFA (replaces the radiation stages of the reference: chi
+ *      core/qed/inline.py:5-13, update_tau_e core/qed/optical_depth.py:38-81, the table lookups
+ *      core/qed/optical_depth_tables.py:32-90, create_photon / photon_recoil core/qed/inline.py:50-117, cpu.py:306-330).
+ *      Two launches around a species' push (csrc/lpa_qed.hip):
+ *
+ *      lpa_qed_event, BEFORE the push: one lane per slot of `p` (any order; `id` must be set).  chi is taken at the
+ *      mid-step position x + c dt/2 u inv_gamma(t) -- the fused kernels' first half push, formed in registers, never
+ *      stored -- from E / B gathered there like lpa_interpolate_2d / _3d and from u(t), inv_gamma(t) (inv_gamma may be
+ *      NULL: LPA_PUSH_NO_IG stores; it is then 1 / sqrt(1 + u^2)).  LPA_QED_STORED_EB: the positions are at mid step
+ *      already and E / B are read from part_eb (the 2-D split path, after lpa_interpolate_2d); `g` is then unused.
+ *      Dead slots and chi < chi_min have no event.  R(chi): `rate`, linear in log10(chi), chi clamped at the last
+ *      node.  EVENT CONTRACT (stateless: no optical-depth row exists, nothing is added to sort, migration or restart):
+ *        (w0, w1, w2, w3) = R(id_lo, id_hi, itime, LPA_QED_PHILOX_TAG) with the generator R and the uniform U of the
+ *        pairing contract of lpa_collide (key = seed); an event fires iff -log(1 - U(w0, w1)) < R(chi) dt inv_gamma --
+ *        the exponential is memoryless, so a fresh optical depth per step has the law of the reference's running one --;
+ *        delta is then sampled with U(w2, w3) by the reference's bisection on `cum` ([chi_n][delta_n], rows blended
+ *        linearly in log10(chi), interpolated in log10(delta)).  The collision draws carry (pair_index << 8 | s) with
+ *        s in 0..3 in the same counter word: a tag whose low byte is 0x10 cannot meet them.
+ *      delta_out[slot] = delta, or 0 without an event; counters[0] += events (one atomic per wave).
+ *
+ *      lpa_qed_emit, AFTER the push and deposit: slots of `p_ele` with delta > 0 that are still alive (a particle
+ *      absorbed at an open face emits nothing) are compacted per wave; the wave reserves its slots behind p_pho->n with
+ *      one atomic on counters[1] (the caller zeroes it, sizes the store for p_pho->n + counters[0] and afterwards
+ *      advances its n by counters[1]); a slot at or beyond photon_capacity is not written and counted in counters[2].
+ *      Photon k (in reservation order): the electron's x y (z) w, u = delta u_e, inv_gamma = 1 / |u|, id = id_base + k,
+ *      is_dead cleared; parent_out[k] (optional) = the electron's id.  The electron recoils: u_e *= 1 - delta,
+ *      inv_gamma (where the array is set) = 1 / sqrt(1 + u_e^2).
+ *
+ *      lpa_push_photons: x += c dt u inv_gamma on every axis of the store, then the periodic fold (pp->wrap bits 0..2,
+ *      lo / hi) and the open-face rule (bits 4..6, alo / ahi: x = y (= z) = NaN, is_dead set) of the fused kernels. */
+#define LPA_QED_PHILOX_TAG 0x51454410u
+#define LPA_QED_STORED_EB 1
+typedef struct {
+    double dt;
+    double chi_factor;               /* e hbar / (m_e^2 c^3) of the host environment's constants */
+    double chi_min;                  /* 10^log_chi_min as the host computes it */
+    const double *rate;              /* [chi_n], chi_n <= 256 (staged in LDS) */
+    const double *cum;               /* [chi_n][delta_n] */
+    int32_t chi_n, delta_n;
+    double log_chi_min, log_chi_max, log_delta_min, log_delta_max;
+    uint64_t seed;
+    uint32_t itime;
+    uint32_t flags;                  /* LPA_QED_* */
+    double *chi_out;                 /* optional diagnostic: chi of every live slot (NULL = not written) */
+} lpa_qed_params;
+int lpa_qed_event(const lpa_grid *g, const lpa_particles *p, const lpa_qed_params *qp, double *delta_out,
+                  uint32_t *counters, void *stream);
+int lpa_qed_emit(const lpa_particles *p_ele, const lpa_particles *p_pho, int64_t photon_capacity, const double *delta,
+                 uint64_t id_base, uint64_t *parent_out, uint32_t *counters, void *stream);
+int lpa_push_photons(const lpa_particles *p, const lpa_push_params *pp, double dt, void *stream);
+
 /* ---- diagnostics the parity contract is stated on (field energy, kinetic energy, total
  *      charge; reference tests/test_numerical_heating.py:19-50).  out[] is device memory and is
  *      accumulated into (zero it first).

@@ -118,6 +118,14 @@ class lpa_collide_params(C.Structure):
                 ("seed", C.c_uint64), ("itime", C.c_uint32), ("pair_index", C.c_uint32), ("skipped", C.c_void_p)]
 
 
+class lpa_qed_params(C.Structure):
+    _fields_ = [("dt", C.c_double), ("chi_factor", C.c_double), ("chi_min", C.c_double), ("rate", C.c_void_p),
+                ("cum", C.c_void_p), ("chi_n", C.c_int32), ("delta_n", C.c_int32), ("log_chi_min", C.c_double),
+                ("log_chi_max", C.c_double), ("log_delta_min", C.c_double), ("log_delta_max", C.c_double),
+                ("seed", C.c_uint64), ("itime", C.c_uint32), ("flags", C.c_uint32), ("chi_out", C.c_void_p)]
+
+
+LPA_QED_PHILOX_TAG, LPA_QED_STORED_EB = 0x51454410, 1
 LPA_COMM_RCCL, LPA_COMM_LOOPBACK = 1, 2
 LPA_STEP_DEFER_E2_GUARDS, LPA_STEP_DEFER_E2, LPA_STEP_E1_DOUBLE = 1, 2, 4
 LPA_STEP_B_EXT_LO, LPA_STEP_B_EXT_HI, LPA_STEP_E_ROUND_IN_LINE, LPA_STEP_SEPARATE_UNPACK, LPA_STEP_SEPARATE_PACK, LPA_STEP_SEPARATE_TAILS = 8, 16, 32, 64, 128, 256
@@ -221,6 +229,9 @@ SIGNATURES = {
     "lpa_collide_debye": (_i, [_G, C.c_int32, C.POINTER(_P), C.POINTER(_T), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                _d, _vp, _vp, _vp, _vp]),
     "lpa_collide": (_i, [_G, _P, _T, _d, _d, _P, _T, _d, _d, C.POINTER(lpa_collide_params), _vp, _i64, _vp]),
+    "lpa_qed_event": (_i, [_G, _P, C.POINTER(lpa_qed_params), _vp, _vp, _vp]),
+    "lpa_qed_emit": (_i, [_P, _P, _i64, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "lpa_push_photons": (_i, [_P, _PP, _d, _vp]),
     "lpa_diag_fields": (_i, [_G, _d, _d, _vp, _vp]),
     "lpa_diag_particles": (_i, [_P, _d, _vp, _vp]),
     "lpa_refresh_inv_gamma": (_i, [_P, _i64, _i64, _vp]),

@@ -67,7 +67,8 @@ class CollisionMixin:
         Coulomb logarithm, every species: the Debye length sums over all of them (`collision.py:153-167`)"""
         st = self.collision
         if st["lnLambda"] <= 0 and any(st["enabled"].values()):
-            return list(range(len(self.species)))
+            photon = getattr(self, "is_photon", lambda i: False)      # (qed.py: photon stores are never sorted)
+            return [i for i in range(len(self.species)) if not photon(i)]
         return sorted({i for p in st["pairs"] if st["enabled"][p] for i in p})
 
     def check_collision(self):

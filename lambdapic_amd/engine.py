@@ -32,6 +32,7 @@ from ._lib import LPA_MIG_NATTR, check, lib
 from .device import DeviceGrid2D, DeviceParticles, current_stream_ptr, restore_device, to_host
 from .dist import MigrateWindowMixin, SlabComm, exchange_faces
 from .collision import CollisionMixin
+from .qed import RadiationMixin
 from .patch import open_face_bounds
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
@@ -130,7 +131,7 @@ class DevicePML2D:
         return self._coef[k]
 
 
-class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin):
+class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin, RadiationMixin):
     dim = 2
 
     def __init__(self, nx, ny, dx, dy, n_guard=3, device="cuda:0", comm: SlabComm | None = None,
@@ -239,11 +240,14 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         return any(self.sort_due(sp) for sp in self.species if sp.n or self.comm.size > 1)
 
     def _rho_forced_sort_due(self):
-        return any(sp.n and (sp.tiling is None or sp.steps_since_sort >= (1 << 29)) for sp in self.species)
+        return any(sp.n and not getattr(sp, "photon", False) and (sp.tiling is None or sp.steps_since_sort >= (1 << 29))
+                   for sp in self.species)
 
     def sort_due(self, sp):
         """the sorter's rule: whenever the store is not tile ordered, and every ``sort_interval`` steps -- or sooner for
         a species whose last intervals ended with a long overflow list (``_adapt_sort_interval``)"""
+        if getattr(sp, "photon", False):        # (qed.py: photons are neither sorted nor deposited)
+            return False
         if self.comm.size > 1:
             # slab chain: ONE clock for all ranks and species (rho.py: neighbouring slabs must re-deposit rho in the same
             # steps, and a sort step is such a step), whatever a rank's own stores look like -- a slab that was empty
@@ -296,7 +300,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     # ---- restart (RestartDump, `callback/restart.py:88-107`: the reference pickles the whole Simulation) ----
     _TRANSIENT = ("L", "_ws", "_halo", "_side", "_axes", "_diag", "_keep", "kernel_events", "_absorbed", "_jx_plane",
-                  "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches")
+                  "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches", "_rad_scratch", "_rad_launches")
 
     def __getstate__(self):
         """everything but handles and scratch: the library handle, sort workspaces (and with them the tilings),
@@ -667,6 +671,49 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
     def _coll_ncells(self):
         return self.nx * self.ny
 
+    # ---- hooks of RadiationMixin (qed.py) ---------------------------------------------------------
+    def _rad_part(self, i, eb):
+        sp = self.species[i]
+        pc = sp.cset.cstruct(sp.n, eb=eb)
+        if sp.ig_stale:
+            pc.inv_gamma = None
+        return pc
+
+    def _rad_capacity(self, i):
+        return self.species[i].capacity
+
+    def _rad_reserve(self, i, capacity):
+        sp = self.species[i]
+        if sp.reserve(capacity):
+            self._ws.pop(id(sp), None)
+
+    def _rad_set_n(self, i, n):
+        self.species[i].n = int(n)
+
+    def _rad_ids(self, i):
+        return self.species[i].cset.id
+
+    def _rad_mark_photon(self, i):
+        self.species[i].photon = True
+
+    def _rad_pp(self, i, dt):
+        sp = self.species[i]
+        pp = _lib.lpa_push_params()
+        pp.dt, pp.wrap = dt, self.local_axes | self.absorb
+        for a in range(3):
+            pp.alo[a], pp.ahi[a] = self.alo[a], self.ahi[a]
+        pp.lo[0], pp.hi[0] = self.x0_global - self.dx / 2, self.x0_global + self.Lx - self.dx / 2
+        pp.lo[1], pp.hi[1] = self.y0 - self.dy / 2, self.y0 + self.Ly - self.dy / 2
+        return pp
+
+    def _rad_id_base(self, i, k):
+        """first of ``k`` fresh ids: one running count per rank and species below bit 50 (``PicEngine3D.new_ids``); a
+        facade that issues ids itself keeps ``radiation["id_next"]`` in step with its own counter"""
+        nxt = self.radiation["id_next"]
+        start = nxt.get(i, 0)
+        nxt[i] = start + int(k)
+        return start + (self.comm.rank << 50)
+
     def _ws_checked(self, sp):
         ws = self._sort_ws(sp)
         if sp.n > sp.capacity:
@@ -701,7 +748,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         (arrival-area) particles -- everything that can deposit into the x guard planes --,
         LPA_PART_INTERIOR the remaining tiles (+ their overflow list)"""
         sp = self.species[ispec]
-        if sp.n == 0:
+        if sp.n == 0 or getattr(sp, "photon", False):
             return
         st = self.stream
         pp = self._push_params(sp, dt)
@@ -1154,7 +1201,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def _species_entries(self, dt, with_mig=False, pushed=False):
         for sp in self.species:
-            if sp.n == 0 and not with_mig:
+            if (sp.n == 0 and not with_mig) or getattr(sp, "photon", False):
                 continue
 
             def after(sp=sp):
@@ -1180,10 +1227,11 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
     def step(self, dt, tiled=True, defer_e2=False):
         """``defer_e2``: leave the E guards to the next step (``run_steps``: nothing reads the fields in between)"""
         self._dt_hint = dt
-        if tiled and self.one_call_step():
+        rad = self.radiation is not None      # (qed.py: the per-stage calls, with the event / emit launches between them)
+        if tiled and not rad and self.one_call_step():
             self.step_fused(dt, defer_e2=defer_e2)
             return
-        if tiled and self.can_fuse() and not self.overlap:
+        if tiled and not rad and self.can_fuse() and not self.overlap:
             self._step_segments(dt, defer_e2)
             return
         E, B = ("ex", "ey", "ez"), ("bx", "by", "bz")
@@ -1198,13 +1246,19 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
             for i, sp in enumerate(self.species):
                 if self.sort_due(sp):
                     self.sort(i)
+        self._radiation_begin()
         self.reset_current()
-        if tiled and self.overlap and self.push_deposit_overlapped(dt):
+        if tiled and not rad and self.overlap and self.push_deposit_overlapped(dt):
             for i in range(len(self.species)):
                 self.sync_particles(i)
         else:
             for i in range(len(self.species)):
+                if rad and self.is_photon(i):
+                    self.push_photons(i, dt)
+                    continue
+                self.radiation_event(i, dt)
                 self.push_deposit(i, dt, tiled=tiled)
+            self.radiation_emit()
             if tiled:
                 self.sync_currents_and_particles()
             else:

@@ -28,6 +28,7 @@ from .engine import PicEngine2D, psi_ptr, psi_rows
 from .fields import FIELD_ATTRS, from_device_layout, to_device_layout
 from .patch import open_face_bounds
 from .collision import CollisionMixin
+from .qed import RadiationMixin
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
 
@@ -119,7 +120,7 @@ class DevicePML3D:
         return self._coef[k]
 
 
-class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin):
+class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin, RadiationMixin):
     dim = 3
     DEFAULT_ORDER = _lib.LPA_ORDER_STRIPED   # the in-tile order new engines sort to (LPA_ORDER_*)
 
@@ -218,11 +219,13 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         return any(self.sort_due(sp) for sp in self.species)     # (an engine without species: nothing to re-deposit)
 
     def _rho_forced_sort_due(self):
-        return any(sp["n"] and (sp["tiling"] is None or sp["since"] >= (1 << 29)) for sp in self.species)
+        return any(sp["n"] and not sp.get("photon") and (sp["tiling"] is None or sp["since"] >= (1 << 29)) for sp in self.species)
 
     def sort_due(self, sp):
         """the sorter's rule: whenever the store is not tile ordered, and every ``sort_interval`` steps -- or sooner for
         a species whose last intervals ended with a long overflow list (see PicEngine2D.overflow_sort_fraction)"""
+        if sp.get("photon"):        # (qed.py: photons are neither sorted nor deposited)
+            return False
         if self.comm.size > 1:      # slab chain: one clock for all ranks and species (PicEngine2D.sort_due)
             return self._chain_clock >= self._chain_interval() or sp["since"] >= (1 << 29)
         return sp["tiling"] is None or sp["since"] >= min(self.sort_interval, sp.get("sort_interval_now", 1 << 30))
@@ -271,7 +274,7 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     # ---- restart (RestartDump, `callback/restart.py:88-107`) ------------------------------------------------
     _TRANSIENT = ("L", "c", "buf", "species", "_halo", "_side", "_axes", "_diag", "_keep", "kernel_events", "_absorbed",
-                  "_jx_plane", "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches")
+                  "_jx_plane", "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches", "_rad_scratch", "_rad_launches")
 
     def __getstate__(self):
         """see PicEngine2D.__getstate__: fields and the slots in use of every store as host arrays, handles,
@@ -281,7 +284,8 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         st = {k: v for k, v in self.__dict__.items() if k not in self._TRANSIENT}
         st["device"], st["buf_host"] = str(self.device), to_host(self.buf)
         st["species_host"] = [{"q": sp["q"], "m": sp["m"], "n": sp["n"], "capacity": int(sp["data"].shape[1]),
-                               "data": to_host(sp["data"][:, : sp["n"]])} for sp in self.species]
+                               "photon": bool(sp.get("photon")), "data": to_host(sp["data"][:, : sp["n"]])}
+                              for sp in self.species]
         return st
 
     def __setstate__(self, st):
@@ -306,7 +310,7 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
             data[:, : h["n"]] = torch.from_numpy(h["data"])
             self.species.append({"q": h["q"], "m": h["m"], "data": data, "c": self._cstruct(data, h["n"]),
                                  "n": h["n"], "n_sorted": 0, "alt": None, "tiling": None, "since": 1 << 30,
-                                 "ws": None})
+                                 "ws": None, "photon": h.get("photon", False)})
 
     @property
     def stream(self):
@@ -423,6 +427,39 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def _coll_ncells(self):
         return self.n[0] * self.n[1] * self.n[2]
+
+    # ---- hooks of RadiationMixin (qed.py) ---------------------------------------------------------
+    def _rad_part(self, i, eb):
+        return self.species[i]["c"]
+
+    def _rad_capacity(self, i):
+        return int(self.species[i]["data"].shape[1])
+
+    def _rad_reserve(self, i, capacity):
+        sp = self.species[i]
+        new = torch.full((NROWS3, int(capacity)), float("nan"), dtype=torch.float64, device=self.device)
+        new[:, : sp["n"]] = sp["data"][:, : sp["n"]]
+        sp["data"], sp["alt"], sp["ws"], sp["tiling"], sp["n_sorted"] = new, None, None, None, 0
+        sp["c"] = self._cstruct(new, sp["n"])
+
+    def _rad_set_n(self, i, n):
+        sp = self.species[i]
+        sp["n"] = int(n)
+        sp["c"] = self._cstruct(sp["data"], sp["n"])
+
+    def _rad_ids(self, i):
+        return self.species[i]["data"][ID_ROW].view(torch.int64)
+
+    def _rad_mark_photon(self, i):
+        self.species[i]["photon"] = True
+
+    def _rad_pp(self, i, dt):
+        return self._push_params(self.species[i], dt)
+
+    def _rad_id_base(self, i, k):
+        start = self._id_next.get(i, 0)
+        self._id_next[i] = start + int(k)
+        return start + (self.comm.rank << 50)
 
     deep_tail_fraction = 0.005   # see PicEngine2D.sort
     sort_lookahead = True
@@ -940,6 +977,8 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         """``part``: LPA_PART_EDGE = edge tile columns + overflow list + arrival area (everything that can
         deposit into the x guard planes), LPA_PART_INTERIOR = the remaining tiles (+ their overflow)"""
         L, st, g, sp = self.L, self.stream, self._g(), self.species[i]
+        if sp.get("photon"):
+            return
         pp = self._push_params(sp, dt)
         if self._no_rho and self.sort_due(sp):
             raise _lib.LpaError("a store needs sorting inside a continuity step: call reset_current() first")
@@ -1039,6 +1078,9 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def _species_entries(self, dt, with_mig=False, pushed=False):
         for sp in self.species:
+            if sp.get("photon"):
+                continue
+
             def after(sp=sp):
                 sp["since"] += 1
 
@@ -1060,10 +1102,11 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         (between the second B half step and its guard sync, simulation.py:1098-1112); ``defer_e2``: see
         PicEngine2D.step"""
         self._dt_hint = dt
-        if self.one_call_step():
+        rad = self.radiation is not None      # (qed.py: the per-stage calls, with the event / emit launches between them)
+        if not rad and self.one_call_step():
             self.step_fused(dt, laser, defer_e2)
             return
-        if self.can_fuse() and self.tiled and not self.overlap:
+        if not rad and self.can_fuse() and self.tiled and not self.overlap:
             self._step_segments(dt, laser, defer_e2)
             return
         L, st, g = self.L, self.stream, self._g()
@@ -1074,10 +1117,18 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         self.update_bfield(0.5 * dt)
         self.sync_guard_fields(2)
         self._collision_stage(dt)
+        self._radiation_begin()
         self.reset_current()
-        if not (self.overlap and self.push_deposit_overlapped(dt)):
+        if not (not rad and self.overlap and self.push_deposit_overlapped(dt)):
             for i in range(len(self.species)):
+                if rad and self.is_photon(i):
+                    self.push_photons(i, dt)
+                    continue
+                if rad and self.tiled and self.sort_due(self.species[i]):
+                    self.sort(i)                 # (the event kernel's delta row is indexed by the slots the push sees)
+                self.radiation_event(i, dt)
                 self.push_deposit(i, dt)
+            self.radiation_emit()
             self.sync_currents()
         for i in range(len(self.species)):
             self.sync_particles(i)

@@ -16,7 +16,7 @@ The device owns the state; ``sim.patches[i].fields.*`` / ``.particles[ispec].*``
 λPIC's layout.  They are refreshed (device -> host) before a stage that has a triggered callback and
 written back (host -> device) after it, so reference-style callbacks run unchanged.  CPML layers,
 laser injection (``lambdapic_amd.laser``) and the moving window are device native.  Out of scope here
-(SURVEY.md section 2): QED, load balancing, I/O.  Binary Coulomb collisions are device native too
+(SURVEY.md section 2): pair production, load balancing, I/O.  Photon emission: ``lambdapic_amd.qed``.  Binary Coulomb collisions are device native too
 (``add_collision``, ``lambdapic_amd.collision``; single slab).  The 3-D twin is ``simulation3d.py``.
 """
 from __future__ import annotations
@@ -28,6 +28,7 @@ import torch
 
 from . import constants
 from .collision import SimulationCollisionMixin
+from .qed import SimulationRadiationMixin
 from .dist import SlabComm
 from .engine import PicEngine2D
 from .patch import make_patches_2d, open_face_bounds
@@ -56,10 +57,27 @@ class Species:
 
 @dataclass
 class Electron(Species):
-    """`core/species.py:185-208` without the radiation / photon links (QED is out of scope)"""
+    """`core/species.py:185-208`: ``radiation="photons"`` with ``photon=`` a ``Photon`` species of the same simulation
+    (or ``set_photon``) turns nonlinear Compton emission on (qed.py); ``radiation="ll"`` is not implemented"""
     name: str = "electron"
     charge: float = field(default=-1, init=False)
     mass: float = field(default=1.0, init=False)
+    radiation: object = None
+    photon: object = None
+
+    def set_photon(self, photon):
+        if self.radiation != "photons":
+            raise ValueError("radiation must be 'photons'")
+        self.photon = photon
+
+
+@dataclass
+class Photon(Species):
+    """`core/species.py:223-243`: moved ballistically, never sorted or deposited (the pair-production links are not
+    implemented)"""
+    name: str = "photon"
+    charge: float = field(default=0, init=False)
+    mass: float = field(default=0.0, init=False)
 
 
 @dataclass
@@ -462,7 +480,7 @@ class MovingWindow:
             sim.shift_window_left(inject)
 
 
-class Simulation(SimulationCollisionMixin):
+class Simulation(SimulationCollisionMixin, SimulationRadiationMixin):
     """2-D periodic simulation driver with the reference's constructor vocabulary
     (`simulation/simulation.py:118-168`) and stage list (`:170-184`)."""
 
@@ -552,6 +570,7 @@ class Simulation(SimulationCollisionMixin):
         self.pusher = [BorisPusher(self, i) for i in range(len(self.species))]
         self.sorter = [ParticleSort2D(self, i) for i in range(len(self.species))]
         self._init_collision()
+        self._init_radiation()
         self.initialized = True
 
     def _next_ids(self, ispec):
@@ -607,6 +626,7 @@ class Simulation(SimulationCollisionMixin):
         nxp, nyp = self.nx_per_patch, self.ny_per_patch
         for s in self.species:
             d = self.engine.species[s.ispec].download()
+            d.update(self._delta_mirror(s.ispec))       # (radiating species: the event kernel's delta row, for '_qed')
             i = np.clip(np.floor((d["x"] - self.engine.x0) / self.dx + 0.5).astype(int) // nxp, 0, self.npatch_x - 1)
             j = np.clip(np.floor(d["y"] / self.dy + 0.5).astype(int) // nyp, 0, self.npatch_y - 1)
             owner = i + j * self.npatch_x
@@ -615,7 +635,9 @@ class Simulation(SimulationCollisionMixin):
                 q = p.particles[s.ispec]
                 q.initialize(int(sel.sum()))
                 for a in d:
-                    if hasattr(q, a):
+                    if a == "delta":
+                        q.delta = d[a][sel]
+                    elif hasattr(q, a):
                         getattr(q, a)[:] = d[a][sel]
 
     def upload(self):
@@ -623,6 +645,7 @@ class Simulation(SimulationCollisionMixin):
         self.engine.grid.upload_patches(list(self.patches), self.npatch_x, self.npatch_y)
         for s in self.species:
             self.engine.species[s.ispec].upload([p.particles[s.ispec] for p in self.patches])
+            self._delta_upload(s.ispec, [p.particles[s.ispec] for p in self.patches])
 
     # ---- the stage loop (`simulation.py:937-1130`) ----------------------------------------------------
     def _triggered(self, cbs):
@@ -706,6 +729,8 @@ class Simulation(SimulationCollisionMixin):
         enabled, the whole stage sequence of this step is enqueued by ONE engine call (``lpa_step``, step.py) -- two when a
         '_laser' callback injects in between.  False: the caller walks the stages one facade call at a time."""
         eng = self.engine
+        if eng.radiation is not None:       # (qed.py: the event / emit launches sit between the per-stage calls)
+            return False
         segments = eng.can_fuse() and eng.comm.size > 1 and not eng.one_call_step() and not eng.overlap
         if not (unified and (eng.one_call_step() or segments)):
             return False
@@ -800,6 +825,7 @@ class Simulation(SimulationCollisionMixin):
             self.patches.sync_guard_fields(B)
             self._run_stage(table, "maxwell_1")
             self.engine._collision_stage(self.dt)      # (`simulation.py:974-978`; nothing without add_collision)
+            self.engine._radiation_begin()
             for ispec in range(len(self.species)):
                 self.ispec = ispec
                 self.sorter[ispec]()
@@ -807,13 +833,17 @@ class Simulation(SimulationCollisionMixin):
             self.current_synced = False
             # no callback between the species' deposits: push the edge tiles first and hide the J / rho
             # exchange behind the interior (the reference's sync_currents_start ... _wait bracket)
-            fused_all = unified and not table.get("current_deposition") and self.engine.overlap and \
+            fused_all = unified and not table.get("current_deposition") and self.engine.radiation is None and self.engine.overlap and \
                 all(p._enabled for p in self.pusher) and self.engine.push_deposit_overlapped(self.dt)
             if fused_all:
                 self.current_synced = True
             for ispec in range(len(self.species) if not fused_all else 0):
                 self.ispec = ispec
-                if unified:
+                if self.engine.is_photon(ispec):         # (`simulation.py:1013-1016`: the photon pusher, no deposit)
+                    if self.pusher[ispec]._enabled:
+                        self.engine.push_photons(ispec, self.dt)
+                elif unified:
+                    self.engine.radiation_event(ispec, self.dt)
                     self.pusher[ispec](self.dt, unified=True)
                     self.current_synced = False      # simulation.py:991: every deposit un-syncs the currents
                 else:
@@ -821,6 +851,8 @@ class Simulation(SimulationCollisionMixin):
                     self._run_stage(table, "_push_position_1")
                     self.interpolator(ispec)
                     self._run_stage(table, "_interpolator")
+                    # chi from the stored ex_part .. bz_part rows at the mid-step position; a '_qed' callback sees delta
+                    self.engine.radiation_event(ispec, self.dt, stored_eb=True)
                     self._run_stage(table, "_qed")
                     self.pusher[ispec](self.dt)
                     self._run_stage(table, "_push_momentum")
@@ -832,6 +864,7 @@ class Simulation(SimulationCollisionMixin):
             self.sync_currents()
             self.ispec = None
             self.patches.sync_particles()
+            self.engine.radiation_emit()               # (`simulation.py:1048-1061`: photons are born, electrons recoil)
             self._run_stage(table, "qed_create_particles")
             self.maxwell.update_bfield(0.5 * self.dt)
             self._run_stage(table, "_laser")

@@ -14,6 +14,7 @@ import torch
 
 from . import constants
 from .collision import SimulationCollisionMixin
+from .qed import SimulationRadiationMixin
 from .dist import SlabComm
 from .engine3d import ATTRS3, NROWS3, SIDES3, PicEngine3D
 from .fields import FIELD_ATTRS, Fields3D, from_device_layout, to_device_layout
@@ -97,7 +98,7 @@ class DevicePatches3D:
             self.sim.engine.sync_particles(i)
 
 
-class Simulation3D(SimulationCollisionMixin):
+class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin):
     STAGES = ["init", "start", "maxwell_1", "_push_position_1", "_interpolator", "_qed", "_push_momentum",
               "_push_position_2", "current_deposition", "qed_create_particles", "_laser", "maxwell_2", "end",
               "final"]
@@ -181,6 +182,7 @@ class Simulation3D(SimulationCollisionMixin):
         self.pusher = [BorisPusher3D(self, i) for i in range(len(self.species))]
         self.sorter = [ParticleSort3D(self, i) for i in range(len(self.species))]
         self._init_collision()
+        self._init_radiation()
         self.initialized = True
 
     def _seed(self, s, org):
@@ -362,22 +364,29 @@ class Simulation3D(SimulationCollisionMixin):
             self.patches.sync_guard_fields(B)
             self._run_stage(table, "maxwell_1")
             eng._collision_stage(self.dt)      # (`simulation.py:974-978`; nothing without add_collision)
+            eng._radiation_begin()
             for ispec in range(len(self.species)):
                 self.sorter[ispec]()
             eng.reset_current()
             self.current_synced = False
-            fused_all = not table.get("current_deposition") and eng.overlap and \
+            fused_all = not table.get("current_deposition") and eng.radiation is None and eng.overlap and \
                 all(p._enabled for p in self.pusher) and eng.push_deposit_overlapped(self.dt)
             if fused_all:
                 self.current_synced = True
             for ispec in range(len(self.species) if not fused_all else 0):
                 self.ispec = ispec
+                if eng.is_photon(ispec):                 # (the photon pusher: no deposit)
+                    if self.pusher[ispec]._enabled:
+                        eng.push_photons(ispec, self.dt)
+                    continue
+                eng.radiation_event(ispec, self.dt)
                 self.pusher[ispec](self.dt, unified=True)
                 self.current_synced = False          # simulation.py:991: every deposit un-syncs the currents
                 self._run_stage(table, "current_deposition")
             self.sync_currents()
             self.ispec = None
             self.patches.sync_particles()
+            eng.radiation_emit()                       # (`simulation.py:1048-1061`)
             self._run_stage(table, "qed_create_particles")
             self.maxwell.update_bfield(0.5 * self.dt)
             self._run_stage(table, "_laser")
