@@ -877,6 +877,40 @@ int lpa_qed_emit(const lpa_particles *p_ele, const lpa_particles *p_pho, int64_t
                  uint64_t id_base, uint64_t *parent_out, uint32_t *counters, void *stream);
 int lpa_push_photons(const lpa_particles *p, const lpa_push_params *pp, double dt, void *stream);
 
+/* ---- Breit-Wheeler pair production, LCFA (replaces the pair stages of the reference: update_tau_gamma
+ *      core/qed/optical_depth.py:87-130, create_pair_inline core/qed/inline.py:120-192, remove_photon_patches
+ *      core/qed/cpu.py:333-347; simulation/simulation.py:993-1030,1062-1065).  Two launches (csrc/lpa_bw.hip):
+ *
+ *      lpa_bw_push_event, IN PLACE OF lpa_push_photons for a pair-producing photon store: one pass, one lane per slot
+ *      (`id` and inv_gamma = 1 / |u| must be set).  chi is taken at the mid-step position x + c dt/2 u inv_gamma, formed
+ *      in registers, from E / B gathered there like lpa_interpolate_2d / _3d (LPA_QED_STORED_EB is rejected).  `qp` is
+ *      an lpa_qed_params whose `rate` and `cum` point at the PAIR tables (delta = the electron's share of the photon's
+ *      energy); dt is qp->dt.  EVENT CONTRACT: that of lpa_qed_event with the counter tag LPA_BW_PHILOX_TAG -- the id
+ *      spaces of species are separate, and with its own tag a photon's draws are also independent of its parent's in
+ *      the step that emitted it.  delta: r = U(w2, w3) (val(delta_n - 1) - val(0)) + val(0) on the blended row
+ *      val(j) = cum[row][j] (1 - t) + cum[row + 1][j] t; j = #{nodes with val(j) < r} - 1 clamped to [0, delta_n - 2]
+ *      (two cooperative rounds of a wave per event; well defined because the blend of two non-decreasing rows is
+ *      non-decreasing, in floating point too; the bisection of lpa_qed_event gives the same j except where a node
+ *      equals r exactly); then log10(delta) is linear between the nodes j and j + 1 (a flat stretch: its left node).
+ *      delta_n <= 4096.  Every live slot is then advanced like lpa_push_photons does (fold pp->wrap bits 0..2, open
+ *      faces bits 4..6): the positions written are the same bits.  A photon absorbed in this step has no event.
+ *      delta_out[slot] = delta, or 0 without an event (every slot below n is written once); counters[0] += events.
+ *
+ *      lpa_bw_create, AFTER the species loop (behind lpa_qed_emit): slots of `p_pho` with delta > 0 that are still
+ *      alive are compacted per wave; the wave reserves k with one atomic on counters[1], and pair k goes to slot
+ *      p_ele->n + k of the electron store and slot p_pos->n + k of the positron store (the loose tails; the caller
+ *      zeroes counters[1], sizes both stores for n + counters[0], afterwards advances both n by counters[1] and forces
+ *      their re-sort).  A slot at or beyond a capacity is not written and counted in counters[2].  Pair k: the photon's
+ *      x y (z) w; u_e = delta u, u_p = (1 - delta) u; inv_gamma = 1 / sqrt(1 + u^2) where the store's array is set;
+ *      ids id_base_ele + k and id_base_pos + k; is_dead cleared; parent_out[k] (optional) = the photon's id.  The photon
+ *      dies: x = y (= z) = NaN, is_dead set where the store has the array.  The three stores have one dimension. */
+#define LPA_BW_PHILOX_TAG 0x42574410u
+int lpa_bw_push_event(const lpa_grid *g, const lpa_particles *p, const lpa_push_params *pp, const lpa_qed_params *qp,
+                      double *delta_out, uint32_t *counters, void *stream);
+int lpa_bw_create(const lpa_particles *p_pho, const lpa_particles *p_ele, const lpa_particles *p_pos, int64_t ele_capacity,
+                  int64_t pos_capacity, const double *delta, uint64_t id_base_ele, uint64_t id_base_pos,
+                  uint64_t *parent_out, uint32_t *counters, void *stream);
+
 /* ---- diagnostics the parity contract is stated on (field energy, kinetic energy, total
  *      charge; reference tests/test_numerical_heating.py:19-50).  out[] is device memory and is
  *      accumulated into (zero it first).

@@ -126,6 +126,7 @@ class lpa_qed_params(C.Structure):
 
 
 LPA_QED_PHILOX_TAG, LPA_QED_STORED_EB = 0x51454410, 1
+LPA_BW_PHILOX_TAG = 0x42574410
 LPA_COMM_RCCL, LPA_COMM_LOOPBACK = 1, 2
 LPA_STEP_DEFER_E2_GUARDS, LPA_STEP_DEFER_E2, LPA_STEP_E1_DOUBLE = 1, 2, 4
 LPA_STEP_B_EXT_LO, LPA_STEP_B_EXT_HI, LPA_STEP_E_ROUND_IN_LINE, LPA_STEP_SEPARATE_UNPACK, LPA_STEP_SEPARATE_PACK, LPA_STEP_SEPARATE_TAILS = 8, 16, 32, 64, 128, 256
@@ -232,6 +233,8 @@ SIGNATURES = {
     "lpa_qed_event": (_i, [_G, _P, C.POINTER(lpa_qed_params), _vp, _vp, _vp]),
     "lpa_qed_emit": (_i, [_P, _P, _i64, _vp, C.c_uint64, _vp, _vp, _vp]),
     "lpa_push_photons": (_i, [_P, _PP, _d, _vp]),
+    "lpa_bw_push_event": (_i, [_G, _P, _PP, C.POINTER(lpa_qed_params), _vp, _vp, _vp]),
+    "lpa_bw_create": (_i, [_P, _P, _P, _i64, _i64, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "lpa_diag_fields": (_i, [_G, _d, _d, _vp, _vp]),
     "lpa_diag_particles": (_i, [_P, _d, _vp, _vp]),
     "lpa_refresh_inv_gamma": (_i, [_P, _i64, _i64, _vp]),

@@ -17,126 +17,13 @@
 //                   photon store, each lane writes its photon and its electron recoils in place.
 //   lpa_push_photons  x += c dt u / |u| with the periodic fold / open-face rule of the fused kernels; no field is read.
 //
-// Every store to memory is a plain vector store or a vector atomic.
-#include "lpa_common.hpp"
+// Every store to memory is a plain vector store or a vector atomic.  The generator, the gather, chi and the photon step
+// are shared with the pair-production kernels (lpa_bw.hip): lpa_qed.hpp.
+#include "lpa_qed.hpp"
 
 namespace {
 
-constexpr int QED_THREADS = 256;
-constexpr int QED_MAX_CHI_N = 256;     // the 1-D rate table staged in LDS: 2 KB
-
-// ---- Philox-4x32-10: the generator and the key / counter convention of lpa_collide.hip (pairing contract of the header)
-struct U4 { uint32_t w[4]; };
-
-__device__ inline U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{{c0, c1, c2, c3}};
-}
-
-__device__ inline double u01(uint32_t lo, uint32_t hi) {
-    return (double)((((uint64_t)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// ---- global-memory gather at a position in cells from node 0: the operations, in the order, of gather_global_2d / _3d
-// (lpa_particles.hip, lpa_particles3d.hip; unified_pusher_2d.c:112-135, unified_pusher_3d.c:111-143,190-195)
-template <bool D3>
-struct GIdx { long r[3]; int c[3]; int d[3]; };
-
-template <bool D3>
-__device__ __forceinline__ void gidx(GIdx<D3> &o, int ix, int iy, int iz, const GridV &g) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        o.r[a] = (long)torus(ix - 1 + a + g.ng, g.NX) * g.NY * g.NZ;
-        o.c[a] = torus(iy - 1 + a + g.ng, g.NY) * g.NZ;
-        o.d[a] = D3 ? torus(iz - 1 + a + g.ng, g.NZ) : 0;
-    }
-}
-
-__device__ __forceinline__ double gather9(const double *__restrict__ f, const GIdx<false> &o, const double fx[3],
-                                          const double fy[3]) {
-    return fy[0] * (fx[0] * f[o.r[0] + o.c[0]] + fx[1] * f[o.r[1] + o.c[0]] + fx[2] * f[o.r[2] + o.c[0]]) +
-           fy[1] * (fx[0] * f[o.r[0] + o.c[1]] + fx[1] * f[o.r[1] + o.c[1]] + fx[2] * f[o.r[2] + o.c[1]]) +
-           fy[2] * (fx[0] * f[o.r[0] + o.c[2]] + fx[1] * f[o.r[1] + o.c[2]] + fx[2] * f[o.r[2] + o.c[2]]);
-}
-
-__device__ __forceinline__ double gather27(const double *__restrict__ f, const GIdx<true> &o, const double fx[3],
-                                           const double fy[3], const double fz[3]) {
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        double pl = 0.0;
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const long b = o.c[j] + o.d[k];
-            pl += fy[j] * (fx[0] * f[o.r[0] + b] + fx[1] * f[o.r[1] + b] + fx[2] * f[o.r[2] + b]);
-        }
-        acc += fz[k] * pl;
-    }
-    return acc;
-}
-
-template <bool D3>
-__device__ __forceinline__ void gather_eb(const GridV &g, double xo, double yo, double zo, double eb[6]) {
-    const int ix1 = ifloor(xo + 0.5), ix2 = ifloor(xo), iy1 = ifloor(yo + 0.5), iy2 = ifloor(yo);
-    double gx[3], hx[3], gy[3], hy[3];
-    tsc3(ix1 - xo, gx); tsc3(ix2 - xo + 0.5, hx);
-    tsc3(iy1 - yo, gy); tsc3(iy2 - yo + 0.5, hy);
-    GIdx<D3> a;
-    if constexpr (!D3) {
-        gidx<false>(a, ix2, iy1, 0, g); eb[0] = gather9(g.ex, a, hx, gy); eb[4] = gather9(g.by, a, hx, gy);
-        gidx<false>(a, ix1, iy2, 0, g); eb[1] = gather9(g.ey, a, gx, hy); eb[3] = gather9(g.bx, a, gx, hy);
-        gidx<false>(a, ix1, iy1, 0, g); eb[2] = gather9(g.ez, a, gx, gy);
-        gidx<false>(a, ix2, iy2, 0, g); eb[5] = gather9(g.bz, a, hx, hy);
-    } else {
-        const int iz1 = ifloor(zo + 0.5), iz2 = ifloor(zo);
-        double gz[3], hz[3];
-        tsc3(iz1 - zo, gz); tsc3(iz2 - zo + 0.5, hz);
-        gidx<true>(a, ix2, iy1, iz1, g); eb[0] = gather27(g.ex, a, hx, gy, gz);
-        gidx<true>(a, ix1, iy2, iz1, g); eb[1] = gather27(g.ey, a, gx, hy, gz);
-        gidx<true>(a, ix1, iy1, iz2, g); eb[2] = gather27(g.ez, a, gx, gy, hz);
-        gidx<true>(a, ix1, iy2, iz2, g); eb[3] = gather27(g.bx, a, gx, hy, hz);
-        gidx<true>(a, ix2, iy1, iz2, g); eb[4] = gather27(g.by, a, hx, gy, hz);
-        gidx<true>(a, ix2, iy2, iz1, g); eb[5] = gather27(g.bz, a, hx, hy, gz);
-    }
-}
-
 // ---- the event kernel ----------------------------------------------------------------------------------------------
-struct QedK {
-    double dt, cdt_half, chi_factor, chi_min;
-    const double *rate, *cum;
-    int chi_n, delta_n;
-    double lc_min, lc_max, dlc, ld_min, dld;
-    uint32_t k0, k1, itime;
-    int stored_eb;
-    double *chi_out;
-};
-
-// calculate_chi_inline (core/qed/inline.py:5-13)
-__device__ __forceinline__ double chi_of(const double eb[6], double ux, double uy, double uz, double ig, double factor) {
-    const double c = LPA_C, gamma = 1.0 / ig;
-    const double fx = gamma * eb[0] + (uy * eb[5] - uz * eb[4]) * c;
-    const double fy = gamma * eb[1] + (uz * eb[3] - ux * eb[5]) * c;
-    const double fz = gamma * eb[2] + (ux * eb[4] - uy * eb[3]) * c;
-    const double ue = ux * eb[0] + uy * eb[1] + uz * eb[2];
-    return factor * sqrt(fx * fx + fy * fy + fz * fz - ue * ue);
-}
-
-// row index and blend weight of log10(chi) in the table: _get_chi_idx (optical_depth_tables.py:32-42), clamped above
-// the last node (there the reference reads one row past its table)
-__device__ __forceinline__ int chi_row(const QedK &k, double chi, double &lc, double &left) {
-    lc = log10(chi);
-    lc = lc > k.lc_max ? k.lc_max : lc;
-    int idx = ifloor((lc - k.lc_min) / k.dlc);
-    idx = idx < 0 ? 0 : (idx > k.chi_n - 2 ? k.chi_n - 2 : idx);
-    left = k.lc_min + idx * k.dlc;
-    return idx;
-}
-
 // _bisect_interp (optical_depth_tables.py:57-90) with the uniform draw `u` in place of np.random.rand(); equality with a
 // node ends the search at that node (the reference loops forever there), and the node index is kept inside the table
 __device__ __forceinline__ double sample_delta(const QedK &k, int row, double t, double u) {
@@ -255,20 +142,6 @@ __global__ void __launch_bounds__(QED_THREADS) k_qed_emit(PartV e, PartV ph, lon
     if (e.ig) e.ig[ip] = 1.0 / sqrt(1 + rx * rx + ry * ry + rz * rz);
 }
 
-// ---- photons move ballistically (the reference's PhotonPusher is a stub: momenta never change) -----------------------
-struct PhotonK {
-    double cdt;
-    int wrap;
-    double lo[3], hi[3], alo[3], ahi[3];
-};
-
-__device__ __forceinline__ double fold(double v, double lo, double hi) {     // sync_particles_2d.c:168-182, self neighbour
-    const double L = hi - lo;
-    if (v > hi) v -= L;
-    if (v < lo) v += L;
-    return v;
-}
-
 template <bool D3>
 __global__ void __launch_bounds__(QED_THREADS) k_push_photons(PartV p, PhotonK k) {
     const long ip = (long)blockIdx.x * QED_THREADS + threadIdx.x;
@@ -276,16 +149,8 @@ __global__ void __launch_bounds__(QED_THREADS) k_push_photons(PartV p, PhotonK k
     if (p.dead && p.dead[ip]) return;
     double r[3] = {p.x[ip], p.y[ip], D3 ? p.z[ip] : 0.0};
     if (isnan(r[0]) || isnan(r[1]) || isnan(r[2])) return;
-    const double s = k.cdt * p.ig[ip];
     const double u[3] = {p.ux[ip], p.uy[ip], p.uz[ip]};
-    bool dead = false;
-#pragma unroll
-    for (int a = 0; a < (D3 ? 3 : 2); a++) {
-        r[a] += s * u[a];
-        if (k.wrap & (1 << a)) r[a] = fold(r[a], k.lo[a], k.hi[a]);
-        dead = dead || ((k.wrap & (LPA_ABSORB_X << a)) && (r[a] < k.alo[a] || r[a] > k.ahi[a]));
-    }
-    if (dead) {                         // mark_out_of_bound_as_dead: beyond an open face
+    if (photon_advance<D3>(k, r, u, p.ig[ip])) {      // mark_out_of_bound_as_dead: beyond an open face
         r[0] = r[1] = r[2] = __longlong_as_double(0x7ff8000000000000ll);
         if (p.dead) p.dead[ip] = 1;
     }
@@ -306,17 +171,9 @@ extern "C" int lpa_qed_event(const lpa_grid *g, const lpa_particles *p, const lp
     LPA_REQUIRE(p->x && p->y && p->ux && p->uy && p->uz && delta_out, "lpa_qed_event: null particle array");
     LPA_REQUIRE(p->id, "lpa_qed_event: the draws are defined on ids: lpa_particles.id must be set");
     LPA_REQUIRE(!stored || p->part_eb[0], "lpa_qed_event: LPA_QED_STORED_EB needs the ex_part .. bz_part rows");
-    LPA_REQUIRE(qp->rate && qp->cum && qp->chi_n >= 2 && qp->chi_n <= QED_MAX_CHI_N && qp->delta_n >= 2 &&
-                    qp->log_chi_max > qp->log_chi_min && qp->log_delta_max > qp->log_delta_min && qp->dt > 0,
-                "lpa_qed_event: bad tables (2 <= chi_n <= %d, delta_n >= 2, ascending ranges)", QED_MAX_CHI_N);
-    QedK k;
-    k.dt = qp->dt; k.cdt_half = LPA_C * 0.5 * qp->dt; k.chi_factor = qp->chi_factor; k.chi_min = qp->chi_min;
-    k.rate = qp->rate; k.cum = qp->cum; k.chi_n = qp->chi_n; k.delta_n = qp->delta_n;
-    k.lc_min = qp->log_chi_min; k.lc_max = qp->log_chi_max;
-    k.dlc = (qp->log_chi_max - qp->log_chi_min) / (qp->chi_n - 1);
-    k.ld_min = qp->log_delta_min; k.dld = (qp->log_delta_max - qp->log_delta_min) / (qp->delta_n - 1);
-    k.k0 = (uint32_t)qp->seed; k.k1 = (uint32_t)(qp->seed >> 32); k.itime = qp->itime;
-    k.stored_eb = stored; k.chi_out = qp->chi_out;
+    LPA_REQUIRE(qed_tables_ok(qp), "lpa_qed_event: bad tables (2 <= chi_n <= %d, delta_n >= 2, ascending ranges)",
+                QED_MAX_CHI_N);
+    const QedK k = make_qedk(qp);
     GridV gv;
     memset(&gv, 0, sizeof gv);
     if (!stored) gv = make_gridv(g, d3 ? 3 : 2);
@@ -353,9 +210,7 @@ extern "C" int lpa_push_photons(const lpa_particles *p, const lpa_push_params *p
     if (p->n == 0) return LPA_OK;
     LPA_REQUIRE(p->x && p->y && p->ux && p->uy && p->uz && p->inv_gamma, "lpa_push_photons: null particle array");
     const bool d3 = p->z != nullptr;
-    PhotonK k;
-    k.cdt = LPA_C * dt; k.wrap = pp->wrap;
-    for (int a = 0; a < 3; a++) { k.lo[a] = pp->lo[a]; k.hi[a] = pp->hi[a]; k.alo[a] = pp->alo[a]; k.ahi[a] = pp->ahi[a]; }
+    const PhotonK k = make_photonk(pp, dt);
     const dim3 grid((unsigned)((p->n + QED_THREADS - 1) / QED_THREADS));
     if (d3) hipLaunchKernelGGL(k_push_photons<true>, grid, dim3(QED_THREADS), 0, (hipStream_t)stream, make_partv(p), k);
     else hipLaunchKernelGGL(k_push_photons<false>, grid, dim3(QED_THREADS), 0, (hipStream_t)stream, make_partv(p), k);

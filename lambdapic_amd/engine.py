@@ -686,9 +686,23 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         sp = self.species[i]
         if sp.reserve(capacity):
             self._ws.pop(id(sp), None)
+            sp.n_sorted, sp.tiling = 0, None     # (as _append_device: the tiling of the old set dies with it)
 
     def _rad_set_n(self, i, n):
         self.species[i].n = int(n)
+
+    def _rad_mass(self, i):
+        return self.species[i].m
+
+    def _rad_arrival_area(self):
+        return self.arrival_area()
+
+    def _rad_appended(self, i):
+        self.species[i].steps_since_sort = 1 << 30
+
+    def _rad_rows(self, i):
+        s = self.species[i].cset
+        return [s.data, s.id] + ([s.eb] if s.eb is not None else [])
 
     def _rad_ids(self, i):
         return self.species[i].cset.id
@@ -1259,6 +1273,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
                 self.radiation_event(i, dt)
                 self.push_deposit(i, dt, tiled=tiled)
             self.radiation_emit()
+            self.bw_create()
             if tiled:
                 self.sync_currents_and_particles()
             else:

@@ -450,6 +450,19 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
     def _rad_ids(self, i):
         return self.species[i]["data"][ID_ROW].view(torch.int64)
 
+    def _rad_mass(self, i):
+        return self.species[i]["m"]
+
+    def _rad_arrival_area(self):
+        return self.arrival_area()
+
+    def _rad_appended(self, i):
+        self.species[i]["since"] = 1 << 30     # (as append_particles: loose particles, rho re-anchored by the re-sort)
+        self._anchor_pending = True
+
+    def _rad_rows(self, i):
+        return [self.species[i]["data"]]
+
     def _rad_mark_photon(self, i):
         self.species[i]["photon"] = True
 
@@ -1129,6 +1142,7 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
                 self.radiation_event(i, dt)
                 self.push_deposit(i, dt)
             self.radiation_emit()
+            self.bw_create()
             self.sync_currents()
         for i in range(len(self.species)):
             self.sync_particles(i)

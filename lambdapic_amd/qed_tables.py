@@ -9,8 +9,16 @@ The cumulative rule is the reference's: the first node is ``quad`` over [0, delt
 left-Riemann step P(delta_i) (delta_i - delta_{i-1}) -- so a row does not end on the total rate, and the sampler
 (csrc/lpa_qed.hip) draws between the row's own first and last node.  The spectrum is evaluated on the whole delta grid at
 once (``scipy.special.airy`` / ``airye`` on arrays); what is left per chi are two ``quad`` calls, well under a minute
-for all 256 rows on one core; ``generate(workers=...)`` spreads the rows over at most 16 fresh interpreters.  The
-pair-production tables and the sigmoid sampling variant of the reference are not part of this module.
+for all 256 rows on one core; ``generate(workers=...)`` spreads the rows over at most 16 fresh interpreters.
+
+The Breit-Wheeler pair tables have the same layout over the photon's chi and the electron's share delta of its energy
+(`optical_depth_tables.py:135-144`; the sampler is csrc/lpa_bw.hip):
+
+    dR/d delta = +(alpha m_e c^2 / hbar) [ Ai1(z) + (2 / z - chi sqrt(z)) Ai'(z) ],   z = (1 / (chi delta (1 - delta)))^(2/3)
+
+The spectrum is symmetric in delta <-> 1 - delta and has no end-point singularity; Ai(z) ~ exp(-8 / (3 chi)) underflows
+to exactly 0 for small chi: such rows are all zeros, and that is valid.  The sigmoid sampling variant of the reference
+is not part of this module.
 """
 from __future__ import annotations
 
@@ -22,6 +30,8 @@ import numpy as np
 CHI_N, LOG_CHI_RANGE = 256, (-3.0, 2.0)
 DELTA_N, LOG_DELTA_RANGE = 1024, (-3.0, 0.0)
 CACHE_PATH = Path(__file__).resolve().parent / "qed_tables_cache.npz"     # next to the built library; not in git
+
+PAIR_KEYS = ("pair_prob_rate_total", "integral_pair_prob_along_delta")
 
 _TABLES = None
 
@@ -56,24 +66,60 @@ def photon_spectrum(chi, delta):
     return np.where(inner, p, 0.0)
 
 
+def pair_spectrum(chi, delta):
+    """dR / d delta (per unit proper time) of a photon with quantum parameter ``chi`` into an electron that takes the
+    share ``delta`` of its energy; ``delta`` scalar or array.  P(0) = P(1) = 0"""
+    from scipy.constants import alpha, c, hbar, m_e
+    from scipy.special import airy
+    delta = np.asarray(delta, dtype=np.float64)
+    inner = (delta > 0.0) & (delta < 1.0)
+    d = np.where(inner, delta, 0.5)
+    with np.errstate(under="ignore"):
+        z = (1.0 / (chi * d * (1.0 - d))) ** (2.0 / 3.0)
+        p = alpha * m_e * c ** 2 / hbar * (airy_tail(z) + (2.0 / z - chi * np.sqrt(z)) * airy(z)[1])
+    return np.where(inner, p, 0.0)
+
+
+def _integral(spectrum, chi, upper, cube, limit=50):
+    """int_0^upper of ``spectrum(chi, .)``; ``cube``: through delta = s^3, which takes a delta^(-2/3) end-point
+    singularity out of the integrand"""
+    from scipy.integrate import quad
+    if cube:
+        return quad(lambda s: 3.0 * s * s * float(spectrum(chi, s ** 3)), 0.0, upper ** (1.0 / 3.0), epsabs=0.0,
+                    epsrel=1e-12, limit=limit)[0]
+    import warnings
+    from scipy.integrate import IntegrationWarning
+    with warnings.catch_warnings():
+        # rows next to the underflow edge: the integrand is a few denormals, of which quad cannot make twelve digits
+        warnings.simplefilter("ignore", IntegrationWarning)
+        return quad(lambda d: float(spectrum(chi, d)), 0.0, upper, epsabs=0.0, epsrel=1e-12, limit=limit)[0]
+
+
 def total_rate(chi):
-    """int_0^1 of the spectrum; delta = s^3 takes the delta^(-2/3) end-point singularity out of the integrand"""
-    from scipy.integrate import quad
-    return quad(lambda s: 3.0 * s * s * float(photon_spectrum(chi, s ** 3)), 0.0, 1.0, epsabs=0.0, epsrel=1e-12, limit=200)[0]
+    """int_0^1 of the photon spectrum"""
+    return _integral(photon_spectrum, chi, 1.0, True, limit=200)
 
 
-def cumulative_row(chi, delta_n=DELTA_N, log_delta_min=LOG_DELTA_RANGE[0]):
-    from scipy.integrate import quad
+def pair_total_rate(chi):
+    """int_0^1 of the pair spectrum (plain ``quad``: no singularity); exactly 0 where the spectrum underflows"""
+    return _integral(pair_spectrum, chi, 1.0, False, limit=200)
+
+
+def cumulative_row(chi, delta_n=DELTA_N, log_delta_min=LOG_DELTA_RANGE[0], spectrum=photon_spectrum):
+    """the reference's rule for either spectrum: ``quad`` up to the first node, then left-Riemann steps"""
     delta = np.logspace(log_delta_min, 0.0, delta_n)
-    steps = photon_spectrum(chi, delta[1:]) * np.diff(delta)
-    first = quad(lambda s: 3.0 * s * s * float(photon_spectrum(chi, s ** 3)), 0.0, delta[0] ** (1.0 / 3.0),
-                 epsabs=0.0, epsrel=1e-12)[0]
+    steps = spectrum(chi, delta[1:]) * np.diff(delta)
+    first = _integral(spectrum, chi, delta[0], spectrum is photon_spectrum)
     return np.concatenate([[first], first + np.cumsum(steps)])
 
 
 def _row(args):
     chi, delta_n, log_delta_min = args
-    return total_rate(chi), cumulative_row(chi, delta_n, log_delta_min)
+    return (total_rate(chi), cumulative_row(chi, delta_n, log_delta_min),
+            pair_total_rate(chi), cumulative_row(chi, delta_n, log_delta_min, pair_spectrum))
+
+
+_ROW_KEYS = ("rate", "cum", "pair_rate", "pair_cum")
 
 
 def _rows_in_workers(jobs, workers):
@@ -99,20 +145,22 @@ def _rows_in_workers(jobs, workers):
                 p.kill()
             return None
         parts = [np.load(os.path.join(tmp, f"rows_{a}.npz")) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
-        return np.concatenate([f["rate"] for f in parts]), np.concatenate([f["cum"] for f in parts])
+        return tuple(np.concatenate([f[k] for f in parts]) for k in _ROW_KEYS)
 
 
 def generate(chi_n=CHI_N, log_chi_range=LOG_CHI_RANGE, delta_n=DELTA_N, log_delta_range=LOG_DELTA_RANGE, workers=1):
-    """dict with the reference's key names (the photon half of ``table_gen``'s file).  ``workers`` > 1: the rows are
+    """dict with the reference's key names (``table_gen``'s file).  ``workers`` > 1: the rows are
     spread over that many fresh interpreters (at most 16); should one of them fail, the rows are computed here"""
     jobs = [(x, delta_n, log_delta_range[0]) for x in np.logspace(log_chi_range[0], log_chi_range[1], chi_n)]
     done = _rows_in_workers(jobs, min(int(workers), 16, chi_n)) if workers > 1 else None
     if done is None:
         rows = [_row(j) for j in jobs]
-        done = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+        done = tuple(np.array([r[k] for r in rows]) for k in range(len(_ROW_KEYS)))
     return {
         "photon_prob_rate_total": done[0],
         "integral_photon_prob_along_delta": done[1],
+        "pair_prob_rate_total": done[2],
+        "integral_pair_prob_along_delta": done[3],
         "chi_N": chi_n, "log_chi_range": tuple(log_chi_range),
         "log_chi_delta": (log_chi_range[1] - log_chi_range[0]) / (chi_n - 1),
         "delta_N": delta_n, "log_delta_range": tuple(log_delta_range),
@@ -121,14 +169,17 @@ def generate(chi_n=CHI_N, log_chi_range=LOG_CHI_RANGE, delta_n=DELTA_N, log_delt
 
 
 def load_tables(path):
-    """read a table file -- this module's cache or one written by the reference's ``table_gen`` (same key names; its
-    pair-production arrays are ignored)"""
+    """read a table file -- this module's cache or one written by the reference's ``table_gen`` (same key names; the
+    pair arrays are read when the file has them)"""
     with np.load(path) as f:
         t = {"photon_prob_rate_total": np.ascontiguousarray(f["photon_prob_rate_total"], dtype=np.float64),
              "integral_photon_prob_along_delta": np.ascontiguousarray(f["integral_photon_prob_along_delta"], dtype=np.float64),
              "chi_N": int(f["chi_N"]), "delta_N": int(f["delta_N"]),
              "log_chi_range": tuple(float(v) for v in f["log_chi_range"]),
              "log_delta_range": tuple(float(v) for v in f["log_delta_range"])}
+        for k in PAIR_KEYS:
+            if k in f.files:
+                t[k] = np.ascontiguousarray(f[k], dtype=np.float64)
     t["log_chi_delta"] = (t["log_chi_range"][1] - t["log_chi_range"][0]) / (t["chi_N"] - 1)
     t["log_delta_delta"] = (t["log_delta_range"][1] - t["log_delta_range"][0]) / (t["delta_N"] - 1)
     if t["photon_prob_rate_total"].shape != (t["chi_N"],) or \
@@ -136,11 +187,22 @@ def load_tables(path):
         raise ValueError(f"{path}: table shapes do not match chi_N / delta_N")
     if not (np.diff(t["integral_photon_prob_along_delta"], axis=1) >= 0).all():      # (flat where the spectrum underflows)
         raise ValueError(f"{path}: a cumulative row decreases")
+    if any(k in t for k in PAIR_KEYS):
+        if not all(k in t for k in PAIR_KEYS) or t[PAIR_KEYS[0]].shape != (t["chi_N"],) or \
+                t[PAIR_KEYS[1]].shape != (t["chi_N"], t["delta_N"]):
+            raise ValueError(f"{path}: pair table shapes do not match chi_N / delta_N")
+        if not (np.diff(t[PAIR_KEYS[1]], axis=1) >= 0).all():      # (all-zero rows where the spectrum underflows)
+            raise ValueError(f"{path}: a cumulative pair row decreases")
     return t
 
 
 def save_tables(path, t):
     np.savez(path, **t)
+
+
+def _has_pair_tables(path):
+    with np.load(path) as f:
+        return all(k in f.files for k in PAIR_KEYS)
 
 
 def tables(path=None, workers=1):
@@ -150,7 +212,7 @@ def tables(path=None, workers=1):
     if path is not None:
         return load_tables(path)
     if _TABLES is None:
-        if not CACHE_PATH.exists():
+        if not CACHE_PATH.exists() or not _has_pair_tables(CACHE_PATH):      # (a cache from before the pair tables)
             tmp = CACHE_PATH.with_suffix(f".{os.getpid()}.tmp.npz")
             save_tables(tmp, generate(workers=workers))
             os.replace(tmp, CACHE_PATH)
@@ -162,4 +224,4 @@ if __name__ == "__main__":      # a worker of generate(): rows [first, stop) of 
     import sys
     _tmp, _a, _b, _dn, _ldm = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), float(sys.argv[5])
     _rows = [_row((x, _dn, _ldm)) for x in np.load(os.path.join(_tmp, "chi.npy"))[_a:_b]]
-    np.savez(os.path.join(_tmp, f"rows_{_a}.npz"), rate=np.array([r[0] for r in _rows]), cum=np.array([r[1] for r in _rows]))
+    np.savez(os.path.join(_tmp, f"rows_{_a}.npz"), **{k: np.array([r[i] for r in _rows]) for i, k in enumerate(_ROW_KEYS)})

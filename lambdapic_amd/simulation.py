@@ -16,7 +16,7 @@ The device owns the state; ``sim.patches[i].fields.*`` / ``.particles[ispec].*``
 λPIC's layout.  They are refreshed (device -> host) before a stage that has a triggered callback and
 written back (host -> device) after it, so reference-style callbacks run unchanged.  CPML layers,
 laser injection (``lambdapic_amd.laser``) and the moving window are device native.  Out of scope here
-(SURVEY.md section 2): pair production, load balancing, I/O.  Photon emission: ``lambdapic_amd.qed``.  Binary Coulomb collisions are device native too
+(SURVEY.md section 2): load balancing, I/O.  Photon emission and pair production: ``lambdapic_amd.qed``.  Binary Coulomb collisions are device native too
 (``add_collision``, ``lambdapic_amd.collision``; single slab).  The 3-D twin is ``simulation3d.py``.
 """
 from __future__ import annotations
@@ -73,18 +73,28 @@ class Electron(Species):
 
 @dataclass
 class Photon(Species):
-    """`core/species.py:223-243`: moved ballistically, never sorted or deposited (the pair-production links are not
-    implemented)"""
+    """`core/species.py:223-243`: moved ballistically, never sorted or deposited.  ``set_bw_pair(electron=, positron=)``
+    (or the two fields) links the species its photons decay into: Breit-Wheeler pair production (qed.py)"""
     name: str = "photon"
     charge: float = field(default=0, init=False)
     mass: float = field(default=0.0, init=False)
+    electron: object = None
+    positron: object = None
+
+    def set_bw_pair(self, *, electron, positron):
+        self.electron, self.positron = electron, positron
 
 
 @dataclass
 class Positron(Species):
+    """`core/species.py:210-214` (``Positron(Electron)``): radiates like an electron -- chi and the emission are
+    charge-blind -- so a cascade closes"""
     name: str = "positron"
     charge: float = field(default=1, init=False)
     mass: float = field(default=1.0, init=False)
+    radiation: object = None
+    photon: object = None
+    set_photon = Electron.set_photon
 
 
 @dataclass
@@ -642,6 +652,7 @@ class Simulation(SimulationCollisionMixin, SimulationRadiationMixin):
 
     def upload(self):
         """``sim.patches`` mirrors -> device (after a callback modified them)"""
+        self.engine.bw_refuse_rebuild()
         self.engine.grid.upload_patches(list(self.patches), self.npatch_x, self.npatch_y)
         for s in self.species:
             self.engine.species[s.ispec].upload([p.particles[s.ispec] for p in self.patches])
@@ -865,6 +876,7 @@ class Simulation(SimulationCollisionMixin, SimulationRadiationMixin):
             self.ispec = None
             self.patches.sync_particles()
             self.engine.radiation_emit()               # (`simulation.py:1048-1061`: photons are born, electrons recoil)
+            self.engine.bw_create()                    # (`simulation.py:1062-1065`: pairs are born, photons die)
             self._run_stage(table, "qed_create_particles")
             self.maxwell.update_bfield(0.5 * self.dt)
             self._run_stage(table, "_laser")

@@ -269,6 +269,7 @@ class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin):
 
     def upload(self):
         eng, g = self.engine, self.n_guard
+        eng.bw_refuse_rebuild()
         npp = self.n_per_patch
         for name in FIELD_ATTRS:
             slab = eng.view(name).cpu().numpy()        # guards outside the mirrors' reach keep their values
@@ -387,6 +388,7 @@ class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin):
             self.ispec = None
             self.patches.sync_particles()
             eng.radiation_emit()                       # (`simulation.py:1048-1061`)
+            eng.bw_create()                            # (`simulation.py:1062-1065`)
             self._run_stage(table, "qed_create_particles")
             self.maxwell.update_bfield(0.5 * self.dt)
             self._run_stage(table, "_laser")
