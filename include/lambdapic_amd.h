@@ -911,6 +911,57 @@ int lpa_bw_create(const lpa_particles *p_pho, const lpa_particles *p_ele, const 
                   int64_t pos_capacity, const double *delta, uint64_t id_base_ele, uint64_t id_base_pos,
                   uint64_t *parent_out, uint32_t *counters, void *stream);
 
+/* ---- particle merging (no reference counterpart; Vranic et al., CPC 191 (2015) 65-73): within a cell, particles that
+ *      share a momentum bin are replaced by two that carry the same weight, momentum and energy.  One launch per
+ *      species: a workgroup per 256-cell tile, a wave per cell, a lane per particle (csrc/lpa_merge.hip).
+ *
+ *      INPUTS: those of lpa_collide -- a store a tile sort has just produced with ahead = 0; only lpa_tiling.tile_off
+ *      is relied on; a particle's cell is the sort's nearest-node cell of its current x, y(, z); `id` must be set
+ *      (LPA_ERR_ARG otherwise) and unique; inv_gamma may be NULL and is never read; NaN-position / is_dead slots are
+ *      ignored; a live particle whose cell is not in its tile is left alone and counted in counters[2].
+ *
+ *      MERGE CONTRACT (a pure function of the set of (id, x, u, w) of each cell: no generator, independent of the
+ *      storage order, restart exact):
+ *       - bin key: s = (ux ux + uy uy) + uz uz, every product and sum rounded on its own (no FMA).  s == 0 or not
+ *         finite: the particle is no candidate.  r = biased exponent of s << radial_bits | the top radial_bits
+ *         mantissa bits of s.  Cube map: the major axis is x if |ux| >= |uy| && |ux| >= |uz|, else y if |uy| >= |uz|,
+ *         else z; face = 2 axis + (u_axis < 0).  The two other components in cyclic order (y z | z x | x y), each
+ *         divided by |u_axis| (IEEE division), give ia, ib = min(angular_bins - 1, (int)floor(((q + 1) * 0.5) *
+ *         angular_bins)).  key = r << 13 | face << 10 | ia << 5 | ib.  No atan2, log or sqrt: a host restatement on the
+ *         integer view of s reproduces the key bit for bit.
+ *       - packets: the candidates of a cell with at least min_per_cell live particles (candidates or not), sorted
+ *         ascending by (key, id); each maximal run of equal key is cut from its start into chunks of max_packet; a
+ *         chunk of at least min_packet members whose weights sum to wt > 0 is a packet, every other chunk is left
+ *         untouched.
+ *       - sums over a packet: wt = sum w, P = sum w u, K = sum w k with k = sqrt(s) when massless, else
+ *         k = s / (1 + sqrt(1 + s)) (the kinetic energy gamma - 1 without its cancellation).  The order of the additions
+ *         is a function of the members' positions in the packet alone (a pairwise tree: at distance d = 1, 2, 4, ...
+ *         the member at an offset that is a multiple of 2 d adds the partial sum of the member at offset + d), so the
+ *         result is the same bits in every run.
+ *       - two survivors: ka = K / wt; pa^2 = ka^2 when massless, else ka (ka + 2); pl = |P| / wt; pperp =
+ *         sqrt(max(pa^2 - pl^2, 0)) (pl <= pa analytically, p(energy) being concave: the clamp guards rounding only);
+ *         e1 = P / |P|, or the signed face axis d if P == 0; e3 = normalize(d - (d . e1) e1), and if that squared norm
+ *         is below 1e-20, with d = the unit vector of the next axis in cyclic order.  The member with the lowest id
+ *         gets u = pl e1 + pperp e3, the second lowest u = pl e1 - pperp e3; both get w = wt / 2, keep their x y (z)
+ *         and id, and inv_gamma (where the array is set) = 1 / |u| when massless, else 1 / sqrt(1 + u^2).  Every other
+ *         member dies as a photon dies in lpa_bw_create: x = y (= z) = NaN, is_dead set where the store has the array.
+ *      Weight and momentum are conserved by construction, energy because both survivors carry |u|^2 = pa^2. */
+typedef struct {
+    int32_t  min_packet;    /* >= 3 */
+    int32_t  max_packet;    /* min_packet .. 64 */
+    int32_t  min_per_cell;  /* cells with fewer live particles are left alone */
+    int32_t  radial_bits;   /* 0 .. 8 */
+    int32_t  angular_bins;  /* 1 .. 32 per cube-face edge */
+    int32_t  massless;      /* 1: photons (energy = |u|), 0: energy = sqrt(1 + u^2) */
+    uint32_t *counters;     /* optional device uint32[4]: [0] += packets merged, [1] += particles removed,
+                               [2] += live particles not in the tile of their cell (skipped) */
+} lpa_merge_params;
+/* bytes of the `workspace` of lpa_merge for a store of these many tile-ordered slots (24 bytes per slot: the cell
+ * lists of (key, id, slot, run start)) */
+int64_t lpa_merge_workspace_bytes(const lpa_grid *g, int64_t capacity);
+int lpa_merge(const lpa_grid *g, const lpa_particles *p, const lpa_tiling *t, const lpa_merge_params *mp,
+              void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---- diagnostics the parity contract is stated on (field energy, kinetic energy, total
  *      charge; reference tests/test_numerical_heating.py:19-50).  out[] is device memory and is
  *      accumulated into (zero it first).

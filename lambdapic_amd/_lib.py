@@ -118,6 +118,11 @@ class lpa_collide_params(C.Structure):
                 ("seed", C.c_uint64), ("itime", C.c_uint32), ("pair_index", C.c_uint32), ("skipped", C.c_void_p)]
 
 
+class lpa_merge_params(C.Structure):
+    _fields_ = [("min_packet", C.c_int32), ("max_packet", C.c_int32), ("min_per_cell", C.c_int32),
+                ("radial_bits", C.c_int32), ("angular_bins", C.c_int32), ("massless", C.c_int32), ("counters", C.c_void_p)]
+
+
 class lpa_qed_params(C.Structure):
     _fields_ = [("dt", C.c_double), ("chi_factor", C.c_double), ("chi_min", C.c_double), ("rate", C.c_void_p),
                 ("cum", C.c_void_p), ("chi_n", C.c_int32), ("delta_n", C.c_int32), ("log_chi_min", C.c_double),
@@ -235,6 +240,8 @@ SIGNATURES = {
     "lpa_push_photons": (_i, [_P, _PP, _d, _vp]),
     "lpa_bw_push_event": (_i, [_G, _P, _PP, C.POINTER(lpa_qed_params), _vp, _vp, _vp]),
     "lpa_bw_create": (_i, [_P, _P, _P, _i64, _i64, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    "lpa_merge_workspace_bytes": (_i64, [_G, _i64]),
+    "lpa_merge": (_i, [_G, _P, _T, C.POINTER(lpa_merge_params), _vp, _i64, _vp]),
     "lpa_diag_fields": (_i, [_G, _d, _d, _vp, _vp]),
     "lpa_diag_particles": (_i, [_P, _d, _vp, _vp]),
     "lpa_refresh_inv_gamma": (_i, [_P, _i64, _i64, _vp]),

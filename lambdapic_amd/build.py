@@ -16,12 +16,13 @@ CSRC = HERE / "csrc"
 LIB = HERE / "liblambdapic_amd.so"
 SOURCES = ["lpa_fields.hip", "lpa_particles.hip", "lpa_particles3d.hip", "lpa_sort.hip", "lpa_patches.hip",
            "lpa_rho.hip", "lpa_step.hip", "lpa_patches3d.hip", "lpa_comm.hip", "lpa_collide.hip", "lpa_qed.hip",
-           "lpa_bw.hip"]
+           "lpa_bw.hip", "lpa_merge.hip"]
 # per-source flags.  lpa_collide.hip is FP64 and integer code throughout: the packed-FP32 target feature is switched off
 # for it so that no v_pk_{add,mul,fma}_f32 can be selected for it whatever a later compiler vectorises (none is needed;
 # the older sources keep the flags they were measured with)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"lpa_collide.hip": _NO_PK_F32, "lpa_qed.hip": _NO_PK_F32, "lpa_bw.hip": _NO_PK_F32}
+SOURCE_FLAGS = {"lpa_collide.hip": _NO_PK_F32, "lpa_qed.hip": _NO_PK_F32, "lpa_bw.hip": _NO_PK_F32,
+                "lpa_merge.hip": _NO_PK_F32}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function"]
 

@@ -32,6 +32,7 @@ from ._lib import LPA_MIG_NATTR, check, lib
 from .device import DeviceGrid2D, DeviceParticles, current_stream_ptr, restore_device, to_host
 from .dist import MigrateWindowMixin, SlabComm, exchange_faces
 from .collision import CollisionMixin
+from .merging import MergingMixin
 from .qed import RadiationMixin
 from .patch import open_face_bounds
 from .rho import RhoContinuityMixin
@@ -131,7 +132,7 @@ class DevicePML2D:
         return self._coef[k]
 
 
-class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin, RadiationMixin):
+class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin, RadiationMixin, MergingMixin):
     dim = 2
 
     def __init__(self, nx, ny, dx, dy, n_guard=3, device="cuda:0", comm: SlabComm | None = None,
@@ -300,7 +301,8 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     # ---- restart (RestartDump, `callback/restart.py:88-107`: the reference pickles the whole Simulation) ----
     _TRANSIENT = ("L", "_ws", "_halo", "_side", "_axes", "_diag", "_keep", "kernel_events", "_absorbed", "_jx_plane",
-                  "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches", "_rad_scratch", "_rad_launches")
+                  "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches", "_rad_scratch", "_rad_launches",
+                  "_merge_scratch", "_merge_launches")
 
     def __getstate__(self):
         """everything but handles and scratch: the library handle, sort workspaces (and with them the tilings),
@@ -561,7 +563,9 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         # thirteen attribute arrays.  The split pusher path has stages between the sort and its interpolation: it asks
         # for them to travel (sort_part_eb).
         ps, pd = src.cstruct(sp.n, eb=self.sort_part_eb), dst.cstruct(dst.capacity, eb=self.sort_part_eb)
-        if self._noig():          # nobody reads the store's inv_gamma before a refresh: the sort need not move it
+        # nobody reads the store's inv_gamma before a refresh: the sort need not move it (a photon store's is 1 / |u|, which
+        # no refresh rebuilds: it travels)
+        if self._noig() and not getattr(sp, "photon", False):
             ps.inv_gamma = pd.inv_gamma = None
             sp.ig_stale = True
         # small stores: smaller work blocks, or a 2 M-particle species is 256 workgroups on 256 CUs (config C3: K1
@@ -670,6 +674,9 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def _coll_ncells(self):
         return self.nx * self.ny
+
+    def _merge_unsorted(self, i):           # (hook of MergingMixin, merging.py)
+        self.species[i].n_sorted, self.species[i].tiling = 0, None
 
     # ---- hooks of RadiationMixin (qed.py) ---------------------------------------------------------
     def _rad_part(self, i, eb):
@@ -1257,6 +1264,7 @@ class PicEngine2D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         self.sync_guard_fields(B)
         if tiled:
             self._collision_stage(dt)
+            self._merging_stage()
             for i, sp in enumerate(self.species):
                 if self.sort_due(sp):
                     self.sort(i)

@@ -28,6 +28,7 @@ from .engine import PicEngine2D, psi_ptr, psi_rows
 from .fields import FIELD_ATTRS, from_device_layout, to_device_layout
 from .patch import open_face_bounds
 from .collision import CollisionMixin
+from .merging import MergingMixin
 from .qed import RadiationMixin
 from .rho import RhoContinuityMixin
 from .step import FusedStepMixin
@@ -120,7 +121,7 @@ class DevicePML3D:
         return self._coef[k]
 
 
-class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin, RadiationMixin):
+class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, CollisionMixin, RadiationMixin, MergingMixin):
     dim = 3
     DEFAULT_ORDER = _lib.LPA_ORDER_STRIPED   # the in-tile order new engines sort to (LPA_ORDER_*)
 
@@ -274,7 +275,8 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     # ---- restart (RestartDump, `callback/restart.py:88-107`) ------------------------------------------------
     _TRANSIENT = ("L", "c", "buf", "species", "_halo", "_side", "_axes", "_diag", "_keep", "kernel_events", "_absorbed",
-                  "_jx_plane", "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches", "_rad_scratch", "_rad_launches")
+                  "_jx_plane", "_one", "_step_keep", "_event_pool", "_coll_scratch", "_coll_launches", "_rad_scratch", "_rad_launches",
+                  "_merge_scratch", "_merge_launches")
 
     def __getstate__(self):
         """see PicEngine2D.__getstate__: fields and the slots in use of every store as host arrays, handles,
@@ -427,6 +429,9 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
 
     def _coll_ncells(self):
         return self.n[0] * self.n[1] * self.n[2]
+
+    def _merge_unsorted(self, i):           # (hook of MergingMixin, merging.py)
+        self.species[i]["n_sorted"], self.species[i]["tiling"] = 0, None
 
     # ---- hooks of RadiationMixin (qed.py) ---------------------------------------------------------
     def _rad_part(self, i, eb):
@@ -1130,6 +1135,7 @@ class PicEngine3D(RhoContinuityMixin, FusedStepMixin, MigrateWindowMixin, Collis
         self.update_bfield(0.5 * dt)
         self.sync_guard_fields(2)
         self._collision_stage(dt)
+        self._merging_stage()
         self._radiation_begin()
         self.reset_current()
         if not (not rad and self.overlap and self.push_deposit_overlapped(dt)):

@@ -5,8 +5,8 @@ csrc/lpa_qed.hip and csrc/lpa_bw.hip, shared by ``PicEngine2D`` and ``PicEngine3
 
 A step with radiation registered runs the per-stage calls (never the one-call ``lpa_step`` route): ``lpa_qed_event`` in
 front of a radiating species' fused push, ``lpa_qed_emit`` behind the last species' deposit, ``lpa_push_photons`` for a
-photon species in place of the Boris push.  Photon species carry no charge: they are left out of the sort, the deposit
-and the rho bookkeeping.  Events are a function of (seed, step, particle id) -- there is no optical-depth array, nothing is
+photon species in place of the Boris push.  Photon species carry no charge: they are left out of the sorter stage (only
+a merge step sorts them, merging.py), the deposit and the rho bookkeeping.  Events are a function of (seed, step, particle id) -- there is no optical-depth array, nothing is
 added to the sort, the migration messages or a checkpoint, and a restart continues exactly.  Two small host reads per
 radiating species and step: the event count (the photon store is grown to hold it before the emit launch, with the
 reference's 25 % slack) and the emitted count (by which the photon store's ``n`` advances).

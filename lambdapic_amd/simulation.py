@@ -28,6 +28,7 @@ import torch
 
 from . import constants
 from .collision import SimulationCollisionMixin
+from .merging import SimulationMergingMixin
 from .qed import SimulationRadiationMixin
 from .dist import SlabComm
 from .engine import PicEngine2D
@@ -490,7 +491,7 @@ class MovingWindow:
             sim.shift_window_left(inject)
 
 
-class Simulation(SimulationCollisionMixin, SimulationRadiationMixin):
+class Simulation(SimulationCollisionMixin, SimulationRadiationMixin, SimulationMergingMixin):
     """2-D periodic simulation driver with the reference's constructor vocabulary
     (`simulation/simulation.py:118-168`) and stage list (`:170-184`)."""
 
@@ -580,6 +581,7 @@ class Simulation(SimulationCollisionMixin, SimulationRadiationMixin):
         self.pusher = [BorisPusher(self, i) for i in range(len(self.species))]
         self.sorter = [ParticleSort2D(self, i) for i in range(len(self.species))]
         self._init_collision()
+        self._init_merging()
         self._init_radiation()
         self.initialized = True
 
@@ -836,6 +838,7 @@ class Simulation(SimulationCollisionMixin, SimulationRadiationMixin):
             self.patches.sync_guard_fields(B)
             self._run_stage(table, "maxwell_1")
             self.engine._collision_stage(self.dt)      # (`simulation.py:974-978`; nothing without add_collision)
+            self.engine._merging_stage()               # (merging.py; nothing without add_merging)
             self.engine._radiation_begin()
             for ispec in range(len(self.species)):
                 self.ispec = ispec

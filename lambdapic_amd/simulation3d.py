@@ -14,6 +14,7 @@ import torch
 
 from . import constants
 from .collision import SimulationCollisionMixin
+from .merging import SimulationMergingMixin
 from .qed import SimulationRadiationMixin
 from .dist import SlabComm
 from .engine3d import ATTRS3, NROWS3, SIDES3, PicEngine3D
@@ -98,7 +99,7 @@ class DevicePatches3D:
             self.sim.engine.sync_particles(i)
 
 
-class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin):
+class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin, SimulationMergingMixin):
     STAGES = ["init", "start", "maxwell_1", "_push_position_1", "_interpolator", "_qed", "_push_momentum",
               "_push_position_2", "current_deposition", "qed_create_particles", "_laser", "maxwell_2", "end",
               "final"]
@@ -182,6 +183,7 @@ class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin):
         self.pusher = [BorisPusher3D(self, i) for i in range(len(self.species))]
         self.sorter = [ParticleSort3D(self, i) for i in range(len(self.species))]
         self._init_collision()
+        self._init_merging()
         self._init_radiation()
         self.initialized = True
 
@@ -365,6 +367,7 @@ class Simulation3D(SimulationCollisionMixin, SimulationRadiationMixin):
             self.patches.sync_guard_fields(B)
             self._run_stage(table, "maxwell_1")
             eng._collision_stage(self.dt)      # (`simulation.py:974-978`; nothing without add_collision)
+            eng._merging_stage()               # (merging.py; nothing without add_merging)
             eng._radiation_begin()
             for ispec in range(len(self.species)):
                 self.sorter[ispec]()

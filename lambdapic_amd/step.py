@@ -146,6 +146,7 @@ class FusedStepMixin:
                     arr[a] = C.pointer(ax)
         if first <= _lib.LPA_STAGE_RESET <= last:
             self._collision_stage(dt)       # (collision.py: nothing unless add_collision was called and a step is due)
+            self._merging_stage()           # (merging.py: likewise for add_merging)
             for i in self.sort_due_species():
                 self.sort(i)
             self._decide_phase()
